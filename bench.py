@@ -15,13 +15,23 @@ after it (returns at once when no wave was deferred), then the summary's two
 launches (partials, + one async RCCL all-reduce of the sums when N > 1).
 value = all ranks' env-steps / max-over-ranks wall time.
 
-Beside it (rank 0, N = 1, untimed for `value`): the per-step API leg
-(`step_api`: 4,194,304 episodes stepped one launch per step from Python by
-BatchedQuadcopterEnv.step_closed, the state round-tripping HBM each step —
-~1.9 GB per step, far beyond the 256 MB Infinity Cache, so the rate is HBM's;
-GB/s against the 8 TB/s HBM peak), the DARE throughput and the CPU baseline.
+A plain run does only that: set-up, warm-up, the K timed steps, the result
+line.  --full adds, beside it (untimed for `value`): the roofline block (this
+run's HIP-event kernel time against the committed rocprofv3 summaries), the
+tracking summary, the DARE throughput and, on rank 0 at N = 1, the per-step
+API leg (`step_api`: 4,194,304 episodes stepped one launch per step from
+Python by BatchedQuadcopterEnv.step_closed, the state round-tripping HBM each
+step — ~1.9 GB per step, far beyond the 256 MB Infinity Cache, so the rate is
+HBM's; GB/s against the 8 TB/s HBM peak) and the CPU baseline with its
+GPU-vs-oracle difference.
 
-Usage: python bench.py [--gpus N] [--steps K] [--warmup W]
+--dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy
+(float64): the per-episode metric rows, the summary partials and the rollout
+state the pass leaves (x, target, t, acc, integ).  The inputs are seeded
+(seeds = global episode index), so two runs with the same arguments write the
+same arrays.  Ranks other than 0 write <name>.rank<r>.npy.
+
+Usage: python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 N > 1 runs one process per GPU under torch.distributed.run: when WORLD_SIZE is
 unset, bench.py starts `python -m torch.distributed.run --nproc-per-node N`
 on itself as a child process (before any GPU call) and exits with its code;
@@ -79,6 +89,11 @@ def parse():
     ap.add_argument("--step-api-steps", type=int, default=100)
     ap.add_argument("--profile-dir", default=PROFILE_DIR,
                     help="committed rocprofv3 summaries (kernel_stats.csv, pmc_*.csv) the line cites")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run and report the side legs: roofline, tracking summary, "
+                         "DARE throughput, per-step API, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float64, at most 64 MB in all)")
     ap.add_argument("--launcher-check", action="store_true",
                     help="CPU plumbing check of the N-rank launch (gloo, no kernels): prints the ranks seen")
     return ap.parse_args()
@@ -226,7 +241,7 @@ def main():
             # (the partials tensor is held until the collective is waited for, so the
             # allocator cannot hand its memory to a later pass while RCCL reads it)
             pending.append((dist.all_reduce(part[0:5], async_op=True), part))
-        return met
+        return met, part
 
     # warm-up: --warmup passes, then chunks of ~0.1 s until --warmup-seconds
     # have run.  Whether to go on is agreed over ranks (MAX) after each chunk,
@@ -261,7 +276,7 @@ def main():
     warmup_s = time.perf_counter() - tw0
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        met = one_pass(True)
+        met, part = one_pass(True)
     for w, _ in pending:
         w.wait()
     pending.clear()
@@ -289,10 +304,87 @@ def main():
     env_steps_per_pass = float(steps_done.item())  # all ranks, executed steps of the last pass
     value = env_steps_per_pass * args.steps / elapsed
 
-    res_summary = None
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, rank, world, {"metrics": met, "state_x": st.x, "state_target": st.target,
+                                                      "state_t": st.t, "state_acc": st.acc, "state_integ": st.integ},
+                     {"summary_partials": part})
+
+    if rank == 0:
+        line = {
+            "metric": "env-steps/sec at 65 536 parallel episodes per GPU (30 s @ dt=0.01, Riccati-LQR closed loop)",
+            "value": round(value, 1),
+            "unit": "env-steps/s",
+            "n_gpus": world,
+            "steps": args.steps,
+            "warmup": args.warmup,
+            "warmup_passes_run": warm,
+            "warmup_s": round(warmup_s, 3),
+            "ms_per_step": round(elapsed / args.steps * 1e3, 4),
+            "higher_is_better": True,
+            "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": "f64",
+            "data": "synthetic: seeded resets, seeds = global episode index; draws made on the GPU by the "
+                    "qt_seed_draws restatement of numpy default_rng (SeedSequence + PCG64 + ziggurat)",
+            "config": {"workload": f"BASELINE configs[1]: {n} episodes/GPU x {nsteps - 2} steps, {args.motion} "
+                                   f"target, Riccati-LQR shared K, RK4 dt=0.01",
+                       "episodes_per_gpu": n, "episodes_total": n * world, "parallelism": f"episode-sharded x{world}"},
+            "kernel_ms": round(kern_ms, 4),
+            "ranks": {"world_size_seen": seen, "backend": "nccl (RCCL)" if world > 1 else None,
+                      "env_steps_per_pass_per_rank": per_rank},
+            "full": args.full,
+        }
+    if args.full:
+        extra = full_legs(args, cfg, dev, rank, world, n, lo, seeds, met, t_dare, local_env_steps, kern_all)
+        if rank == 0:
+            line.update(extra)
+    if rank == 0:
+        print(json.dumps(line), flush=True)
+    if world > 1:
+        dist.destroy_process_group()
+
+
+# the most --dump-outputs writes over all ranks
+DUMP_BYTES_MAX = 64 * 1000 * 1000
+
+
+def dump_outputs(out_dir, rank, world, per_episode, whole):
+    """Write the last timed pass's results as float64 .npy files: `per_episode`
+    tensors ([rows, n] or [n]) and the small `whole` tensors.  When this rank's
+    share of DUMP_BYTES_MAX cannot hold every episode, the per-episode arrays
+    keep a fixed sample of columns (seeded, sorted; the same for every array
+    and every run), whose indices go to episode_index.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    suffix = ".npy" if rank == 0 else f".rank{rank}.npy"
+    arrays = {k: v.detach().cpu().numpy().astype(np.float64, copy=False) for k, v in whole.items()}
+    # this rank's share, less the small arrays and room for every file's header
+    budget = DUMP_BYTES_MAX // world - sum(a.nbytes for a in arrays.values())
+    budget -= 4096 * (len(per_episode) + len(whole) + 1)
+    n = next(iter(per_episode.values())).shape[-1]
+    rows = sum(int(np.prod(v.shape[:-1])) for v in per_episode.values()) + 1  # + the index row
+    keep = None
+    if rows * n * 8 > budget:
+        keep = np.sort(np.random.default_rng(0).choice(n, size=max(1, budget // (rows * 8)), replace=False))
+    arrays["episode_index"] = (np.arange(n) if keep is None else keep).astype(np.float64)
+    for k, v in per_episode.items():
+        a = v.detach().cpu().numpy().astype(np.float64, copy=False)
+        arrays[k] = a if keep is None else np.ascontiguousarray(a[..., keep])
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, k + suffix), a)
+
+
+def full_legs(args, cfg, dev, rank, world, n, lo, seeds, met, t_dare, local_env_steps, kern_all):
+    """--full: what the bench reports beside the headline figure (untimed for
+    `value`): tracking summary, DARE throughput, per-step API leg, CPU baseline
+    and the roofline block.  Every rank calls it (the summary is a collective
+    when N > 1); returns the result line's extra keys."""
+    import torch
+
+    from quadtrack.controllers import BatchedRiccatiLQR
     from quadtrack.parallel import summary_from_partials
     from quadtrack.utils.metrics import SuccessCriteria
 
+    kern_ms = float(np.mean(kern_all))
     res_summary = summary_from_partials(met, SuccessCriteria(), global_offset=lo)
 
     # ---- DARE throughput (per-episode gains, config-4 style), reported beside
@@ -352,25 +444,7 @@ def main():
             i_ach = i_flops / (kern_ms * 1e-3) / 1e12
             issued_line = {"flops_per_launch": i_flops, "per_env_step": round(i_flops / local_env_steps, 2),
                            "source": i_src, "counters_per_launch": i_counts}
-        line = {
-            "metric": "env-steps/sec at 65 536 parallel episodes per GPU (30 s @ dt=0.01, Riccati-LQR closed loop)",
-            "value": round(value, 1),
-            "unit": "env-steps/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "warmup_passes_run": warm,
-            "warmup_s": round(warmup_s, 3),
-            "ms_per_step": round(elapsed / args.steps * 1e3, 4),
-            "higher_is_better": True,
-            "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": "f64",
-            "data": "synthetic: seeded resets, seeds = global episode index; draws made on the GPU by the "
-                    "qt_seed_draws restatement of numpy default_rng (SeedSequence + PCG64 + ziggurat)",
-            "config": {"workload": f"BASELINE configs[1]: {n} episodes/GPU x {nsteps - 2} steps, {args.motion} "
-                                   f"target, Riccati-LQR shared K, RK4 dt=0.01",
-                       "episodes_per_gpu": n, "episodes_total": n * world, "parallelism": f"episode-sharded x{world}"},
+        return {
             "roofline": {"bound": "valu", "achieved": round(achieved, 3), "peak": FP64_PEAK_TFLOPS,
                          "unit": "TFLOP/s", "frac": round(achieved / FP64_PEAK_TFLOPS, 4),
                          "traffic": None if traffic is None else round(traffic),
@@ -387,16 +461,12 @@ def main():
                          "issued_frac": None if issued is None else round(i_ach / FP64_PEAK_TFLOPS, 4),
                          "issued": issued_line,
                          "profiled": prof_line},
-            "ranks": {"world_size_seen": seen, "backend": "nccl (RCCL)" if world > 1 else None,
-                      "env_steps_per_pass_per_rank": per_rank},
             "cpu_baseline": cpu,
             "tracking": track,
             "dare": dare,
             "step_api": step_api,
         }
-        print(json.dumps(line), flush=True)
-    if world > 1:
-        dist.destroy_process_group()
+    return None
 
 
 # HBM bytes per env-step the per-step API's closed step must move by its

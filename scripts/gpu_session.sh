@@ -8,8 +8,8 @@
 # steps:
 #   tests      pytest -m gpu (PYTEST_ARGS narrows it)
 #   smoke      __graft_entry__.smoke()
-#   bench      bench.py with the driver's defaults (BENCH_ARGS adds flags)
-#   benchab    bench.py at --steps 20 --warmup 5 and --steps 100 --warmup 20 (steadiness)
+#   bench      bench.py --full with its default steps (BENCH_ARGS adds flags)
+#   benchab    bench.py --full at --steps 20 --warmup 5 and --steps 100 --warmup 20 (steadiness)
 #   workloads  scripts/run_workload.py for CONFIGS (default "3 4 5")
 #   dare       scripts/dare_bench.py (structured + dense DARE throughput)
 #   ab         scripts/ab.sh on LIBS (library builds, "tree" = in-tree) via perf_sweep
@@ -38,9 +38,9 @@ for step in ${STEPS:-tests smoke bench}; do
            tail -3 $O/tests.log ;;
     smoke) timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1 || fail smoke $O/smoke.log
            tail -1 $O/smoke.log ;;
-    bench) timeout -k 10 600 python bench.py ${BENCH_ARGS:-} > $O/bench.json 2> $O/bench.err || fail bench $O/bench.err ;;
-    benchab) timeout -k 10 300 python bench.py --steps 20 --warmup 5 > $O/bench_s20_w5.json 2> $O/benchab.err || fail benchab $O/benchab.err
-             timeout -k 10 300 python bench.py --steps 100 --warmup 20 --no-cpu-baseline > $O/bench_s100_w20.json 2>> $O/benchab.err \
+    bench) timeout -k 10 600 python bench.py --full ${BENCH_ARGS:-} > $O/bench.json 2> $O/bench.err || fail bench $O/bench.err ;;
+    benchab) timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 > $O/bench_s20_w5.json 2> $O/benchab.err || fail benchab $O/benchab.err
+             timeout -k 10 300 python bench.py --full --steps 100 --warmup 20 --no-cpu-baseline > $O/bench_s100_w20.json 2>> $O/benchab.err \
                || fail benchab $O/benchab.err ;;
     workloads) for c in ${CONFIGS:-3 4 5}; do
                  timeout -k 10 300 python -u scripts/run_workload.py --config $c --repeat 10 >> $O/workloads.jsonl 2>> $O/workloads.err \
