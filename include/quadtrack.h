@@ -35,7 +35,7 @@
 extern "C" {
 #endif
 
-#define QT_ABI_VERSION 9
+#define QT_ABI_VERSION 10
 
 /* error codes */
 #define QT_OK 0
@@ -230,6 +230,27 @@ enum qt_frame_flag {
 };
 #define QT_FRAME_BYTES(n) ((int64_t)(n) * (QT_FR_ROWS * 8 + QT_FC_ROWS * 8 + QT_FB_ROWS))
 
+/* ABI 10.  Lean frame: the part of a frame that is state.  One contiguous
+   device block of QT_LEAN_BYTES(n) bytes (8-byte aligned):
+     double  f[QT_LR_ROWS][n]   rows below (state, reward)
+     int32_t c[QT_FC_ROWS][n]   the counters of qt_frame_count
+     int8_t  b[QT_FB_ROWS][n]   the flags of qt_frame_flag
+   Everything else a frame holds is a function of (pattern, step count,
+   state, counters) and is built on demand by qt_lean_expand, bit for bit
+   what the full-frame entry points store: the target observation and the
+   time from the step count and the time table (below), the tracking error
+   as -reward, the on-target ratio from two counters.
+   Bytes per env-step of a closed-loop step on lean frames (shared structured
+   LQR gain, linear target, freeze_done), counted as the full frame's 462 B
+   are: in 96 (state) + 12 (counters) + 1 (done flag) + 24 (pattern draw),
+   out 121 (the lean frame: 104 + 12 + 5) + 32 (the command) = 286 B. */
+enum qt_lean_row {
+  QT_LR_X = 0,            /* 12 rows, as QT_FR_X */
+  QT_LR_REWARD = 12,      /* reward = -||p - p_T|| after the step (the reset state's at reset) */
+  QT_LR_ROWS = 13
+};
+#define QT_LEAN_BYTES(n) ((int64_t)(n) * (QT_LR_ROWS * 8 + QT_FC_ROWS * 4 + QT_FB_ROWS))
+
 /* ---------------------------------------------------------------- entry points */
 
 /* ABI version of the loaded library. */
@@ -410,6 +431,51 @@ int qt_compute_action_obs(const qt_ctrl_params* ctrl, const qt_batch* batch, con
 int qt_frame_closed_step(const qt_env_params* env, const qt_ctrl_params* ctrl, const qt_batch* batch,
                          const void* in, double* integ, void* out, double* action, int32_t freeze_done,
                          void* stream);
+
+/* ---- ABI 10: the per-step API on lean frames ------------------------------
+   The twins of qt_frame_reset / qt_frame_step / qt_frame_closed_step that
+   read and write lean frames (qt_lean_row above, QT_LEAN_BYTES(n)), with the
+   same arithmetic: every value equals what the full-frame entry point
+   computes, bit for bit.  Asynchronous on `stream`; batch->order must be NULL;
+   n == 0 returns QT_OK before any frame, table or action pointer is read.
+
+   Time table.  A lean frame stores no time.  Every episode is reset to t = 0
+   and every step adds the same dt, so an episode's time is a function of its
+   step count: the DEVICE array ttab[len] with ttab[0] = 0.0 and
+   ttab[k + 1] = fl(ttab[k] + dt) (the host's accumulation; one table serves
+   every episode and every step) holds at ttab[step] exactly the time the full
+   frame carries.  A step reads ttab[step] (the observation's time) and
+   ttab[step + 1] (the time after it).  max_step is the caller's bound on
+   every episode's step count before the call; max_step < 0 or
+   max_step + 1 >= len is QT_EINVAL.  The kernels also clamp the index to
+   len - 1, so a wrong bound cannot read out of range. */
+
+/* qt_frame_reset into a lean frame: x = [p_target(0) + offset, 0...], the
+   reward of the reset state, counters and flags 0. */
+int qt_lean_reset(const qt_env_params* env, const qt_batch* batch, const double* offset, void* lean,
+                  void* stream);
+
+/* qt_frame_closed_step from lean frame `in` to lean frame `out` (in == out
+   allowed): the observation's target is formed at ttab[step] as the full
+   frame's was stored, then compute_action (integ updated) and env.step.
+   action[4][n] (may be NULL) receives the command; freeze_done as
+   qt_frame_closed_step. */
+int qt_lean_closed_step(const qt_env_params* env, const qt_ctrl_params* ctrl, const qt_batch* batch,
+                        const double* ttab, int64_t len, int64_t max_step, const void* in, double* integ,
+                        void* out, double* action, int32_t freeze_done, void* stream);
+
+/* qt_frame_step (open loop, an action view) from lean frame `in` to lean
+   frame `out` (in == out allowed). */
+int qt_lean_step(const qt_env_params* env, const qt_batch* batch, const double* ttab, int64_t len,
+                 int64_t max_step, const void* in, qt_view action, void* out, int32_t freeze_done,
+                 void* stream);
+
+/* The full frame (QT_FRAME_BYTES(n)) of a lean one: state rows, reward and
+   flags copied; target rows built at ttab[step]; time = ttab[step];
+   tracking error = -reward (exact; a NaN's sign flips back); on-target ratio
+   = on / step (0 at step 0); counters widened to int64. */
+int qt_lean_expand(const qt_env_params* env, const qt_batch* batch, const double* ttab, int64_t len,
+                   const void* lean, void* frame, void* stream);
 
 /* TargetMotion.get_state(t) (target_motion.py:387-411) for every episode at
    per-episode times t[n]: out[9][n] = position, velocity, clamped acceleration. */

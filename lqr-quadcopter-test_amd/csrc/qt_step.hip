@@ -1,4 +1,5 @@
-// qt_step.hip — the per-step API (include/quadtrack.h, ABI 9): one batched
+// qt_step.hip — the per-step API (include/quadtrack.h, ABI 9; the lean
+// frame's twins of these kernels: qt_step_lean.hip): one batched
 // env.step, compute_action or closed-loop step per launch.
 //
 // The fused rollout (qt_kernels.hpp) keeps an episode in registers for a
@@ -19,9 +20,9 @@
 // 0.57 of HBM at 1,048,576 episodes; fewer registers spill, a lighter step
 // needs more of them).
 // Reference functions: src/quadcopter_tracking/... of the reference repo.
-#include "qt_kernels.hpp"
+#include "qt_step.hpp"
 
-using namespace qtk;
+using namespace qts;
 
 namespace {
 
@@ -36,8 +37,6 @@ __device__ __forceinline__ FrameDev frame_of(const void* base, int64_t n) {
   return FrameDev{f, reinterpret_cast<int64_t*>(f + QT_FR_ROWS * n),
                   reinterpret_cast<int8_t*>(f + (QT_FR_ROWS + QT_FC_ROWS) * n)};
 }
-
-__device__ __forceinline__ double view_at(const qt_view& v, int r, int64_t e) { return v.p[r * v.rs + e * v.es]; }
 
 // An episode that is done and frozen carries its frame over unchanged.
 __device__ __forceinline__ void copy_column(const FrameDev& I, const FrameDev& O, int64_t n, int64_t ep) {
@@ -58,60 +57,17 @@ __device__ __forceinline__ void store_target(const FrameDev& O, int64_t n, int64
   }
 }
 
-// Counters carried from frame to frame (info["step"], info["action_violations"],
-// the env's on-target count).
-struct Counts {
-  int64_t step, viol, on;
-};
-
-// An episode's per-launch inputs outside the frame: motion type, target
-// pattern, plant.  Loaded with everything else before any data-dependent
-// branch, so that a step waits for memory once (DESIGN §3 "Per-step API").
-struct EpisodeIn {
-  int motion;
-  Pattern pt;
-  Plant pl;
-};
-
-__device__ __forceinline__ EpisodeIn episode_in(const qt_env_params& e, const BatchDev& b, int64_t ep) {
-  const int motion = motion_of(b, e, ep);
-  return EpisodeIn{motion, pattern_of(b, e, motion, ep), make_plant(e, b.plant_mass ? b.plant_mass[ep] : e.mass)};
-}
-
-// QuadcopterEnv.step (quadcopter_env.py:152-232) of episode ep from state x
-// at time t with the raw action u, into frame O: _parse_and_validate_action
-// (234-293), _integrate (295-327), _apply_state_constraints (428-465),
-// t += dt (191), observation (472-496), reward (504-511), termination
-// (513-535), on-target count (204-207), info (209-226), success (537-553).
-__device__ __forceinline__ void env_step_into(const qt_env_params& e, const EpisodeIn& in, int64_t n, int64_t ep,
-                                              double* x, double t, Counts k, const double* u, const FrameDev& O) {
-  const int motion = in.motion;
-  const Pattern& pt = in.pt;
-  const Plant& pl = in.pl;
-  double ua[4];
-  // The rows that depend on time only (the target observation, time, step
-  // count) first: their stores drain while the step computes, which shortens
-  // a small batch's launch (one wave per SIMD: load, compute, store in
-  // series; 65,536 episodes 9.0 -> 8.0-8.7 us, profiles/r06/step_kernel_ab_r06_early.jsonl).
-  // Every load of the step precedes this (in == out steps in place).
-  t += e.dt;
-  Target tg;
-  target_state<true>(e, motion, pt, t, tg);
+// env_step_into's stores into the full frame (qt_step.hpp): every value is kept.
+__device__ __forceinline__ void store_early(const FrameDev& O, int64_t n, int64_t ep, const Target& tg, double t,
+                                            int64_t step) {
   store_target(O, n, ep, tg);
   O.f[QT_FR_TIME * n + ep] = t;
-  O.c[QT_FC_STEP * n + ep] = k.step + 1;
-  const bool viol = parse_action(e, u, ua);
-  integrate(e, pl, x, ua);
-  // np.clip's NaN propagation kept: a caller's action may drive the state anywhere
-  const int term = constrain_terminate<true>(e, x, t);
-  const double q0 = x[0] - tg.p[0], q1 = x[1] - tg.p[1], q2 = x[2] - tg.p[2];
-  const double err = sqrt(dot3_blas(q0, q1, q2));  // float(np.linalg.norm(quad_pos - target_pos))
-  const bool on = err <= e.target_radius;
-  k.step += 1;
-  k.viol += viol;
-  k.on += on;
-  const double ratio = (double)k.on / (double)k.step;
-  const bool success = !(t < e.min_episode_duration) && ratio >= e.min_on_target_ratio;
+  O.c[QT_FC_STEP * n + ep] = step;
+}
+
+__device__ __forceinline__ void store_late(const FrameDev& O, int64_t n, int64_t ep, const double* x, double err,
+                                           double ratio, const Counts& k, int term, bool on, bool viol,
+                                           bool success) {
 #pragma unroll
   for (int i = 0; i < 12; ++i) O.f[(QT_FR_X + i) * n + ep] = x[i];
   O.f[QT_FR_ERR * n + ep] = err;
@@ -124,41 +80,6 @@ __device__ __forceinline__ void env_step_into(const qt_env_params& e, const Epis
   O.b[QT_FB_VIOLATION * n + ep] = viol;
   O.b[QT_FB_SUCCESS * n + ep] = success;
   O.b[QT_FB_TERM * n + ep] = (int8_t)term;
-}
-
-// The controller of one episode: RiccatiLQRController / LQRController
-// (compute_action) or PIDController (compute_action_pid, observation time
-// `now`).  KS (the caller asserts the structured gain pattern): the six
-// (nine) per-axis gains are read, which equals K s exactly for a finite s;
-// a non-finite observation or integral takes the dense product, whose
-// 0 * NaN terms the reference's K @ s has (riccati_lqr.py:864-900).
-template <int KC, bool KS>
-using CtlGains = Gains<KC, KC == 3 || KS>;
-
-template <int KC, bool FF, bool KS>
-__device__ __forceinline__ bool control(const qt_ctrl_params& c, const BatchDev& b, int64_t ep,
-                                        const CtlGains<KC, KS>& G, double hover, const double* qp, const double* qv,
-                                        const Target& tg, double now, const FFLane& fl, double* in, double* u) {
-  if constexpr (KC == 3) {
-    compute_action_pid<FF>(c, G.k, hover, qp, qv, tg, now, fl, in, u);
-    return false;
-  } else if constexpr (KS) {
-    double s = ((qp[0] + qp[1]) + (qp[2] + qv[0])) + ((qv[1] + qv[2]) + (tg.p[0] + tg.p[1])) +
-               ((tg.p[2] + tg.v[0]) + (tg.v[1] + tg.v[2]));
-    if (KC == 9) s += (in[0] + in[1]) + in[2];
-    if (__builtin_expect(isfinite(s), 1)) return compute_action<KC, FF, true>(c, G, hover, qp, qv, tg, fl, in, u);
-    Gains<KC, false> D;
-    load_gains<KC, false>(b, ep, D);
-    return compute_action<KC, FF, false>(c, D, hover, qp, qv, tg, fl, in, u);
-  } else {
-    return compute_action<KC, FF, false>(c, G, hover, qp, qv, tg, fl, in, u);
-  }
-}
-
-// integral / controller-state rows: LQI 3, PID 4 (integral error + last time)
-template <int KC>
-constexpr int integ_rows() {
-  return KC == 9 ? 3 : (KC == 3 ? 4 : 0);
 }
 
 // ------------------------------------------------------------------ reset
@@ -216,7 +137,7 @@ __global__ __launch_bounds__(kBlock) void frame_step_kernel(qt_env_params e, Bat
     if (!inplace) copy_column(I, O, n, ep);
     return;
   }
-  env_step_into(e, ei, n, ep, x, t, k, u, O);
+  env_step_into(e, ei, n, ep, x, t + e.dt, k, u, O);
 }
 
 // --------------------------------------------------- controller on a view
@@ -305,23 +226,10 @@ __global__ __launch_bounds__(kBlock) void closed_step_kernel(qt_env_params e, qt
 #pragma unroll
     for (int i = 0; i < 4; ++i) action[i * n + ep] = u[i];
   }
-  env_step_into(e, ei, n, ep, x, t, k, u, O);
+  env_step_into(e, ei, n, ep, x, t + e.dt, k, u, O);
 }
 
 // ------------------------------------------------------------- dispatch
-
-// Calls L::template run<KC, FF, KS>() for a runtime (kc, ff, ks); PID (kc 3)
-// is per-axis by construction.
-template <class L>
-int dispatch_ctl(int kc, bool ff, bool ks, L& l) {
-  if (kc == 3) return ff ? l.template run<3, true, true>() : l.template run<3, false, true>();
-  if (kc == 9) {
-    if (ff) return ks ? l.template run<9, true, true>() : l.template run<9, true, false>();
-    return ks ? l.template run<9, false, true>() : l.template run<9, false, false>();
-  }
-  if (ff) return ks ? l.template run<6, true, true>() : l.template run<6, true, false>();
-  return ks ? l.template run<6, false, true>() : l.template run<6, false, false>();
-}
 
 struct ActionObsLaunch {
   hipStream_t s;
@@ -358,8 +266,6 @@ struct ClosedLaunch {
     return check_launch();
   }
 };
-
-bool valid_view(const qt_view& v) { return v.p != nullptr; }
 
 }  // namespace
 

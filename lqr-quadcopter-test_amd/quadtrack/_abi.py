@@ -15,7 +15,7 @@ import torch
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # QUADTRACK_LIB points timing experiments (scripts/ablate.sh) at another build
 LIB_PATH = os.environ.get("QUADTRACK_LIB") or os.path.join(_HERE, "_lib", "libquadtrack.so")
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 # enums (include/quadtrack.h)
 MOTIONS = ("stationary", "linear", "circular", "sinusoidal", "figure8")
@@ -103,11 +103,22 @@ def frame_bytes(n: int) -> int:
     return n * (FR_ROWS * 8 + FC_ROWS * 8 + FB_ROWS)
 
 
+# lean frame (qt_lean_row, ABI 10): f [LR_ROWS][n] float64, c [FC_ROWS][n] int32, b [FB_ROWS][n] int8
+LR_ROWS = 13
+LR_X, LR_REWARD = 0, 12
+
+
+def lean_bytes(n: int) -> int:
+    """QT_LEAN_BYTES(n)"""
+    return n * (LR_ROWS * 8 + FC_ROWS * 4 + FB_ROWS)
+
+
 EXPORTS = ("qt_abi_version", "qt_host_alloc", "qt_host_free", "qt_stream_sync", "qt_seed_draws", "qt_seed_uniform", "qt_reset", "qt_rollout", "qt_rollout_rewards", "qt_rollout_grouped", "qt_rollout_fresh",
            "qt_env_step", "qt_compute_action", "qt_target_state",
            "qt_episode_metrics", "qt_metrics_from_arrays", "qt_dare_batched", "qt_dare_dense", "qt_summary",
            "qt_summary_parts", "qt_summary_numpy", "qt_stream_uniform", "qt_frame_reset", "qt_frame_step",
-           "qt_compute_action_obs", "qt_frame_closed_step")
+           "qt_compute_action_obs", "qt_frame_closed_step", "qt_lean_reset", "qt_lean_closed_step", "qt_lean_step",
+           "qt_lean_expand")
 
 _lib = None
 
@@ -154,6 +165,10 @@ def load():
     L.qt_frame_step.argtypes = [P(EnvParams), P(Batch), vp, View, vp, i32, vp]
     L.qt_compute_action_obs.argtypes = [P(CtrlParams), P(Batch), P(ObsView), vp, vp, vp, vp]
     L.qt_frame_closed_step.argtypes = [P(EnvParams), P(CtrlParams), P(Batch), vp, vp, vp, vp, i32, vp]
+    L.qt_lean_reset.argtypes = [P(EnvParams), P(Batch), vp, vp, vp]
+    L.qt_lean_closed_step.argtypes = [P(EnvParams), P(CtrlParams), P(Batch), vp, i64, i64, vp, vp, vp, vp, i32, vp]
+    L.qt_lean_step.argtypes = [P(EnvParams), P(Batch), vp, i64, i64, vp, View, vp, i32, vp]
+    L.qt_lean_expand.argtypes = [P(EnvParams), P(Batch), vp, i64, vp, vp, vp]
     for name in EXPORTS[1:]:
         getattr(L, name).restype = C.c_int
     v = L.qt_abi_version()

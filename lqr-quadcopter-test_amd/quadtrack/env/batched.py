@@ -22,6 +22,11 @@ through a small pool of frames.  The next step reads its state from the last
 frame, so writing into the returned tensors in place would change the
 environment: the env detects that (the views share one version counter) and
 raises instead.
+
+`lean=True` (ABI 10) runs the same calls on lean frames (qt_lean_reset /
+qt_lean_step / qt_lean_closed_step: 286 B instead of 462 B per closed-loop
+env-step) and builds what a lean frame does not hold on first use
+(qt_lean_expand); see the class doc.
 """
 
 from __future__ import annotations
@@ -32,8 +37,8 @@ import numpy as np
 import torch
 
 from .. import _abi, core
-from .._abi import FB_DONE, FR_X, MOTIONS, check, on_device, raw_stream
-from ..step import Frame, FramePool, action_tensor
+from .._abi import FB_DONE, FC_STEP, FR_X, MOTIONS, check, on_device, raw_stream
+from ..step import Frame, FramePool, LeanFrame, LeanSource, TimeTable, action_tensor
 from . import seeding
 from .config import as_env_config
 
@@ -76,12 +81,22 @@ class BatchedQuadcopterEnv:
                 Evaluator stops stepping at done, eval.py:119-165); False:
                 every episode is stepped on every call, as the reference's
                 env steps after done.
+    lean        False (default): every step writes a full observation frame
+                (229 B per episode).  True: steps read and write lean frames
+                (quadtrack.step.LeanFrame: state, reward, counters, flags,
+                121 B per episode; qt_lean_* of ABI 10) with the same results
+                bit for bit.  reward, done, info["action"] and
+                obs["quadcopter"] are served from the lean frame; the first
+                read of anything else a step returned (obs["target"],
+                obs["time"], obs.frame, any other info value) expands that
+                step's full frame, one launch (`expand_launches` counts them).
     """
 
     STATE_DIM = 12
     ACTION_DIM = 4
 
-    def __init__(self, num_envs: int, config=None, device=None, motion=None, mass=None, freeze_done: bool = True):
+    def __init__(self, num_envs: int, config=None, device=None, motion=None, mass=None, freeze_done: bool = True,
+                 lean: bool = False):
         if num_envs < 0:
             raise ValueError("num_envs must be >= 0")
         self.config = as_env_config(config)
@@ -97,7 +112,15 @@ class BatchedQuadcopterEnv:
         self.pattern: torch.Tensor | None = None
         self.offset: torch.Tensor | None = None
         self._frame: Frame | None = None
-        self._pool = FramePool(self.num_envs, self.device)  # the frames steps write
+        self.lean = bool(lean)
+        self._pool = FramePool(self.num_envs, self.device, kind=LeanFrame if self.lean else None)  # the frames steps write
+        self._expands = [0]  # qt_lean_expand launches (LeanSource.count)
+        if self.lean:
+            # the time table (quadtrack.h ABI 10): an episode's length in steps plus slack; extended on demand
+            p = self.params
+            self._table = TimeTable(p.dt, int(np.ceil(p.max_episode_time / p.dt)) + 3, dev)
+            self._steps = 0  # steps since reset: the bound on every episode's step count
+            self._source: LeanSource | None = None
         self._env_ref = C.byref(self.params)
         self._batch = None
         self._closed = None  # (controller, its qt_batch, byref) of step_closed
@@ -120,10 +143,17 @@ class BatchedQuadcopterEnv:
         self._closed = None
         self._frame = None
         fr = self._next_frame()
+        reset = _abi.load().qt_lean_reset if self.lean else _abi.load().qt_frame_reset
         with torch.cuda.device(dev):
-            check(_abi.load().qt_frame_reset(self._env_ref, self._batch_ref, self.offset.data_ptr(), fr.ptr,
-                                             raw_stream(dev)), "qt_frame_reset")
+            check(reset(self._env_ref, self._batch_ref, self.offset.data_ptr(), fr.ptr, raw_stream(dev)),
+                  "qt_lean_reset" if self.lean else "qt_frame_reset")
         self._frame = fr.seal()
+        if self.lean:
+            self._steps = 0
+            self._source = LeanSource(self._env_ref, self._batch_ref,
+                                      (self.params, b, self.pattern, self.motion, self.plant_mass), self._table, dev,
+                                      self._expands)
+            return fr.observation(self._source)
         return fr.observation()
 
     def reset(self, seeds=None):
@@ -158,6 +188,8 @@ class BatchedQuadcopterEnv:
         fr = self._current()
         n, dev = self.num_envs, self.device
         a = action_tensor(actions, n, dev)
+        if self.lean:
+            return self._lean_step(fr, a)
         out = self._next_frame()
         with on_device(dev):
             check(_abi.load().qt_frame_step(self._env_ref, self._batch_ref, fr.ptr,
@@ -179,6 +211,8 @@ class BatchedQuadcopterEnv:
             raise ValueError(f"the controller is on {controller.device}, the environment on {dev}")
         cb = self._closed_batch(controller)
         integ = controller._state_for(n)
+        if self.lean:
+            return self._lean_step_closed(fr, controller, cb, integ)
         out = self._next_frame()
         with on_device(dev):
             check(_abi.load().qt_frame_closed_step(
@@ -186,6 +220,38 @@ class BatchedQuadcopterEnv:
                 out.ptr, out.act_ptr, int(self.freeze_done), raw_stream(dev)), "qt_frame_closed_step")
         self._frame = out.seal()
         return out.step_result(with_action=True)
+
+    def _lean_step(self, fr: LeanFrame, a: torch.Tensor):
+        """step on lean frames (qt_lean_step)."""
+        dev, tab = self.device, self._table
+        tab.cover(self._steps)
+        out = self._next_frame()
+        with on_device(dev):
+            check(_abi.load().qt_lean_step(self._env_ref, self._batch_ref, tab.ptr, tab.len, self._steps, fr.ptr,
+                                           _abi.View(a.data_ptr(), a.stride(1), a.stride(0)), out.ptr,
+                                           int(self.freeze_done), raw_stream(dev)), "qt_lean_step")
+        self._steps += 1
+        self._frame = out.seal()
+        return out.step_result(self._source)
+
+    def _lean_step_closed(self, fr: LeanFrame, controller, cb, integ):
+        """step_closed on lean frames (qt_lean_closed_step)."""
+        dev, tab = self.device, self._table
+        tab.cover(self._steps)
+        out = self._next_frame()
+        with on_device(dev):
+            check(_abi.load().qt_lean_closed_step(
+                self._env_ref, controller._ctrl_ref, cb, tab.ptr, tab.len, self._steps, fr.ptr,
+                None if integ is None else integ.data_ptr(), out.ptr, out.act_ptr, int(self.freeze_done),
+                raw_stream(dev)), "qt_lean_closed_step")
+        self._steps += 1
+        self._frame = out.seal()
+        return out.step_result(self._source, with_action=True)
+
+    @property
+    def expand_launches(self) -> int:
+        """qt_lean_expand launches since construction (0 for a default env)."""
+        return self._expands[0]
 
     def _closed_batch(self, controller):
         """qt_batch of the env's episodes with the controller's gains (cached)."""
@@ -202,7 +268,8 @@ class BatchedQuadcopterEnv:
     # ---------------------------------------------------------- observation
     def observation(self) -> dict:
         """The current observation (views of the last frame)."""
-        return self._current().observation()
+        fr = self._current()
+        return fr.observation(self._source) if self.lean else fr.observation()
 
     @property
     def done(self) -> torch.Tensor:
@@ -217,18 +284,23 @@ class BatchedQuadcopterEnv:
         x = torch.as_tensor(x, dtype=F64, device=self.device)
         if x.shape != (self.num_envs, self.STATE_DIM):
             raise ValueError(f"State must have shape ({self.num_envs}, {self.STATE_DIM}), got {tuple(x.shape)}")
-        out = Frame(self.num_envs, self.device)
+        out = (LeanFrame if self.lean else Frame)(self.num_envs, self.device)
         out.buf.copy_(fr.buf)
         out.f[FR_X:FR_X + 12].copy_(x.T)
         self._frame = out.seal()
 
     @property
     def frame(self) -> Frame:
-        return self._current()
+        """The last step's Frame (a lean env expands it on first use)."""
+        fr = self._current()
+        return self._source.frame_of(fr) if self.lean else fr
 
     @property
     def time(self) -> torch.Tensor:
-        return self._current().f[_abi.FR_TIME].clone()
+        fr = self._current()
+        if self.lean:  # an episode's time is the table's entry at its step count
+            return self._table.dev[fr.c[FC_STEP].long()]
+        return fr.f[_abi.FR_TIME].clone()
 
     @property
     def dt(self) -> float:

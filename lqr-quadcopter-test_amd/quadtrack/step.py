@@ -23,6 +23,15 @@ launch over the batch, and what it returns is views, not copies.
 A closed-loop step through the two plugin calls is two launches
 (qt_compute_action_obs, qt_frame_step); `BatchedQuadcopterEnv.step_closed`
 is one (qt_frame_closed_step).
+
+* Lean frames (ABI 10, `BatchedQuadcopterEnv(lean=True)`): a `LeanFrame`
+  holds only what is state (qt_lean_row: the 12-state, the reward, int32
+  counters, the flags; 121 B per episode against 229 B), held and recycled
+  by the same rules (`_Block`).  Everything else a step returns is lazy
+  (`LazyObservation`, `LazyInfo`): the first read expands the step's full
+  `Frame` in one launch (`LeanSource.frame_of`, qt_lean_expand), with the
+  values the full-frame path stores, bit for bit.  Time is not stored: it is
+  `TimeTable`'s entry at the episode's step count.
 """
 
 from __future__ import annotations
@@ -34,8 +43,8 @@ import numpy as np
 import torch
 
 from . import _abi
-from ._abi import (FB_DONE, FB_ROWS, FB_TERM, FC_ROWS, FR_ROWS, FR_TIME, Batch, ObsView, View, check, on_device,
-                   raw_stream)
+from ._abi import (FB_DONE, FB_ROWS, FB_TERM, FC_ROWS, FR_ROWS, FR_TIME, LR_REWARD, LR_ROWS, Batch, ObsView, View,
+                   check, lean_bytes, on_device, raw_stream)
 
 F64 = torch.float64
 
@@ -66,19 +75,75 @@ def _stor_uses(stor) -> int:
     return torch._C._storage_Use_Count(stor._cdata)
 
 
-class Frame:
+class _Block:
+    """What the two frame layouts (Frame, LeanFrame) share: one device
+    allocation `buf` — the frame's rows f / c / b, then the [4, n] command
+    rows of a closed-loop step (`act`) — the write seal, and the
+    hold-and-recycle test.
+
+    The tensors a step hands out are built once per frame (`_views`, by the
+    layout's `_build_views`).  A frame is `recyclable` — a later step may
+    write it again — only when nothing outside holds any of it: every
+    handed-out view is back to the Python reference count the frame itself
+    holds, and no other tensor (a slice, a reshape) shares its storage.  So
+    a caller that keeps an observation, a reward, an info value or a view
+    derived from one keeps it unchanged, as with a fresh frame; a loop that
+    drops them lets the env cycle through two frames without allocating or
+    building views."""
+
+    __slots__ = ("n", "buf", "f", "c", "b", "act", "ptr", "act_ptr", "version", "_views", "_refs", "_uses", "_stor")
+
+    def _adopt(self, n: int, buf: torch.Tensor) -> None:
+        """Take the allocation (the layout has set f / c / b / act on it)."""
+        self.n = n
+        self.buf = buf
+        self.ptr = buf.data_ptr()
+        self.act_ptr = self.act.data_ptr()
+        # the buffer's storage object, held for its use count (_stor_uses)
+        self._stor = buf.untyped_storage() if _CAN_RECYCLE else None
+        self.version = None  # buf._version once a kernel has written it (seal)
+        self._views = None
+
+    def seal(self):
+        """Mark the frame as written: a later in-place change of any of its views
+        (which share the buffer's version counter) is detected by `check_intact`."""
+        self.version = self.buf._version
+        return self
+
+    def check_intact(self) -> None:
+        if self.buf._version != self.version:
+            raise RuntimeError("the observation of the last step was modified in place; its tensors are views of "
+                               "the environment state (clone() them before writing into them)")
+
+    def _handed_out(self):
+        """The views a step hands out, built once and counted (`_snapshot`)."""
+        if self._views is None:
+            self._build_views()
+            self._snapshot()
+        return self._views
+
+    def _counts(self):
+        return list(map(sys.getrefcount, self._views))
+
+    def _snapshot(self):
+        # what the frame itself holds (called with no other reference alive)
+        self._refs = self._counts()
+        self._uses = _stor_uses(self._stor)
+
+    def recyclable(self) -> bool:
+        """True when no view of this frame is held outside it (see the class doc)."""
+        return (self._views is not None and _CAN_RECYCLE and _stor_uses(self._stor) == self._uses
+                and self._counts() == self._refs)
+
+    def reuse(self) -> None:
+        """Called by the pool when a later step takes the frame to write it again."""
+
+
+class Frame(_Block):
     """One step's observation + info block (qt_frame_row): f [25, n] float64,
     c [3, n] int64, b [5, n] int8 views of one device allocation, followed
-    by the [4, n] command rows of a closed-loop step (`act`).
-
-    The tensors a step hands out are built once per frame (`_views`).  A
-    frame is `recyclable` — a later step may write it again — only when
-    nothing outside holds any of it: every handed-out view is back to the
-    Python reference count the frame itself holds, and no other tensor
-    (a slice, a reshape) shares its storage.  So a caller that keeps an
-    observation, a reward, an info value or a view derived from one keeps
-    it unchanged, as with a fresh frame; a loop that drops them lets the
-    env cycle through two frames without allocating or building views.
+    by the [4, n] command rows of a closed-loop step (`act`).  Held and
+    recycled as _Block describes.
 
     What a held tensor pins: every reward, done, info or observation tensor
     is a view of the whole frame, so holding one keeps the frame's
@@ -89,38 +154,20 @@ class Frame:
     view: 65,536 episodes x 3,000 steps of held views would pin ~51 GB where
     clones take ~1.5 GB."""
 
-    __slots__ = ("n", "buf", "f", "c", "b", "act", "ptr", "act_ptr", "version", "_q", "_obs_view", "_views",
-                 "_refs", "_uses", "_info", "_stor")
+    __slots__ = ("_q", "_obs_view", "_info")
 
     def __init__(self, n: int, device):
-        self.n = n
         fw = frame_words(n)
-        self.buf = torch.empty(fw + 4 * n, dtype=F64, device=device)
-        f, c, b, a = self.buf.split([FR_ROWS * n, FC_ROWS * n, fw - (FR_ROWS + FC_ROWS) * n, 4 * n])
+        buf = torch.empty(fw + 4 * n, dtype=F64, device=device)
+        f, c, b, a = buf.split([FR_ROWS * n, FC_ROWS * n, fw - (FR_ROWS + FC_ROWS) * n, 4 * n])
         self.f = f.view(FR_ROWS, n)
         self.c = c.view(torch.int64).view(FC_ROWS, n)
         self.b = b.view(torch.int8)[:FB_ROWS * n].view(FB_ROWS, n)
         self.act = a.view(4, n)
-        self.ptr = self.buf.data_ptr()
-        self.act_ptr = self.act.data_ptr()
-        # the buffer's storage object, held for its use count (_stor_uses)
-        self._stor = self.buf.untyped_storage() if _CAN_RECYCLE else None
-        self.version = None  # buf._version once a kernel has written it (seal)
+        self._adopt(n, buf)
         self._q = None
         self._obs_view = None
-        self._views = None
         self._info = None
-
-    def seal(self) -> "Frame":
-        """Mark the frame as written: a later in-place change of any of its views
-        (which share the buffer's version counter) is detected by `check_intact`."""
-        self.version = self.buf._version
-        return self
-
-    def check_intact(self) -> None:
-        if self.buf._version != self.version:
-            raise RuntimeError("the observation of the last step was modified in place; its tensors are views of "
-                               "the environment state (clone() them before writing into them)")
 
     # --------------------------------------------------------------- views
     def _quantities(self):
@@ -132,8 +179,7 @@ class Frame:
 
     def observation(self) -> Observation:
         if self._views is None:
-            self._build_views()
-            self._snapshot()
+            self._handed_out()
         q = self._q
         obs = Observation(quadcopter={"position": q[0], "velocity": q[1], "attitude": q[2],
                                       "angular_velocity": q[3]},
@@ -154,18 +200,10 @@ class Frame:
         # every tensor a step hands out: reward, done, the command, the observation, the info values
         self._views = (rew, done, self.act.T) + q + tuple(v for _, v in self._info)
 
-    def _counts(self):
-        return list(map(sys.getrefcount, self._views))
-
-    def _snapshot(self):
-        # what the frame itself holds (called with no other reference alive)
-        self._refs = self._counts()
-        self._uses = _stor_uses(self._stor)
-
-    def recyclable(self) -> bool:
-        """True when no view of this frame is held outside it (see the class doc)."""
-        return (self._views is not None and _CAN_RECYCLE and _stor_uses(self._stor) == self._uses
-                and self._counts() == self._refs)
+    def info_items(self):
+        """((key, [n] tensor), ...) of the info dict, in the reference's key order."""
+        self._handed_out()
+        return self._info
 
     def step_result(self, with_action: bool = False):
         """(obs, reward [n], done [n] bool, info) of QuadcopterEnv.step
@@ -202,17 +240,222 @@ class Frame:
             return False
 
 
+def lean_words(n: int) -> int:
+    """float64 elements of a lean frame of n episodes (QT_LEAN_BYTES rounded up)."""
+    return (lean_bytes(n) + 7) // 8
+
+
+def time_table(dt: float, length: int, prefix: np.ndarray | None = None) -> np.ndarray:
+    """The time table of quadtrack.h (ABI 10): t[0] = 0.0, t[k + 1] = fl(t[k] + dt),
+    the accumulation `t += dt` of every episode (quadcopter_env.py:191), so
+    t[step] is an episode's time bit for bit.  `prefix`: an earlier table
+    to continue (kept as it is)."""
+    if prefix is None:
+        prefix = np.zeros(1)
+    if length <= prefix.size:
+        return prefix
+    # ufunc.accumulate is the sequential recurrence r[i] = r[i-1] + a[i]
+    tail = np.add.accumulate(np.concatenate([prefix[-1:], np.full(length - prefix.size, float(dt))]))[1:]
+    return np.concatenate([prefix, tail])
+
+
+class TimeTable:
+    """An env's time table on its device: `cover(max_step)` makes
+    ttab[max_step + 1] exist (the entry a step of an episode at max_step
+    reads) by continuing the accumulation, so an extended table keeps its
+    prefix bit for bit; `ptr` / `len` are what the qt_lean_* calls take."""
+
+    def __init__(self, dt: float, length: int, device):
+        self.dt, self.device = float(dt), device
+        self._set(time_table(self.dt, max(int(length), 2)))
+
+    def _set(self, host: np.ndarray) -> None:
+        self.host = host
+        self.dev = torch.from_numpy(host).to(self.device)
+        self.len, self.ptr = host.size, self.dev.data_ptr()  # plain attributes: read once per step
+
+    def cover(self, max_step: int) -> None:
+        if max_step + 1 >= self.len:
+            self._set(time_table(self.dt, max(2 * self.len, max_step + 2), self.host))
+
+
+_LAZY = object()  # a lazy container's entry that is not built yet
+
+
+class _LazyItems:
+    """The part of a lean step's observation / info dict that the lean frame
+    does not hold.  The keys are there from the start (keys(), `in`,
+    iteration and len() are the full dict's and touch nothing); the first
+    read of such an entry's value materialises the step's full frame
+    (`source.frame_of(lean)`: one qt_lean_expand, shared by the step's
+    observation and info) and fills every entry with that frame's views."""
+
+    __slots__ = ()
+
+    def _fill(self) -> None:
+        if not self._filled:
+            self._filled = True
+            for k, v in self._lazy_items(self._source.frame_of(self._lean)):
+                if dict.get(self, k) is _LAZY:  # not replaced or deleted by the caller meanwhile
+                    dict.__setitem__(self, k, v)
+
+    def __getitem__(self, k):
+        v = dict.__getitem__(self, k)
+        if v is _LAZY:
+            self._fill()
+            v = dict.__getitem__(self, k)
+        return v
+
+    def get(self, k, default=None):
+        return self[k] if k in self else default
+
+    def __iter__(self):  # a Python-level __iter__: dict(obs) and {**obs} read through keys() / __getitem__
+        return dict.__iter__(self)
+
+    def _filled_method(name):
+        def method(self, *a, **kw):
+            self._fill()
+            return getattr(dict, name)(self, *a, **kw)
+
+        method.__name__ = name
+        return method
+
+    for _name in ("values", "items", "copy", "pop", "popitem", "setdefault", "__eq__", "__ne__", "__repr__", "__or__",
+                  "__ror__"):
+        locals()[_name] = _filled_method(_name)
+    del _name, _filled_method
+
+
+class LazyObservation(_LazyItems, Observation):
+    """A lean step's observation: obs["quadcopter"][...] are views of the lean
+    frame; obs["target"], obs["time"] and obs.frame come from the step's full
+    frame, built on first use (_LazyItems)."""
+
+    __slots__ = ("_lean", "_source", "_filled")
+
+    def __init__(self, quadcopter: dict, lean, source):
+        dict.__init__(self, quadcopter=quadcopter, target=_LAZY, time=_LAZY)
+        self._lean, self._source, self._filled = lean, source, False
+
+    @staticmethod
+    def _lazy_items(fr):
+        o = fr.observation()
+        return ("target", o["target"]), ("time", o["time"])
+
+    @property
+    def frame(self):
+        """The step's full Frame (materialised on first use)."""
+        return self._source.frame_of(self._lean)
+
+
+INFO_KEYS = ("time", "step", "tracking_error", "on_target", "on_target_ratio", "action_violations",
+             "termination_code", "episode_length", "success", "violation", "on_target_count")
+
+
+class LazyInfo(_LazyItems, dict):
+    """A lean step's info dict: info["action"] (a closed-loop step) is a view
+    of the lean frame's command rows, every other value comes from the step's
+    full frame on first use (_LazyItems)."""
+
+    __slots__ = ("_lean", "_source", "_filled")
+
+    _UNBUILT = dict.fromkeys(INFO_KEYS, _LAZY)
+
+    def __init__(self, lean, source, action=None):
+        dict.__init__(self, self._UNBUILT)
+        if action is not None:
+            dict.__setitem__(self, "action", action)
+        self._lean, self._source, self._filled = lean, source, False
+
+    @staticmethod
+    def _lazy_items(fr):
+        return fr.info_items()
+
+
+class LeanFrame(_Block):
+    """One step's lean frame (qt_lean_row, ABI 10): f [13, n] float64 (state,
+    reward), c [3, n] int32, b [5, n] int8 views of one device allocation
+    (QT_LEAN_BYTES(n), 121 B per episode), followed by the [4, n] command rows
+    of a closed-loop step.  Held and recycled as _Block describes: reward,
+    done, the command and the four quadcopter observation tensors are its
+    views.  `full` is the step's full Frame once something asked for it
+    (LeanSource.frame_of); a materialised Frame belongs to whoever holds it
+    and is never written again."""
+
+    __slots__ = ("full",)
+
+    def __init__(self, n: int, device):
+        w = lean_words(n)
+        buf = torch.empty(w + 4 * n, dtype=F64, device=device)
+        raw = buf[:w].view(torch.uint8)
+        c0, b0 = LR_ROWS * 8 * n, (LR_ROWS * 8 + FC_ROWS * 4) * n
+        self.f = buf[:LR_ROWS * n].view(LR_ROWS, n)
+        self.c = raw[c0:b0].view(torch.int32).view(FC_ROWS, n)
+        self.b = raw[b0:lean_bytes(n)].view(torch.int8).view(FB_ROWS, n)
+        self.act = buf[w:].view(4, n)
+        self._adopt(n, buf)
+        self.full = None
+
+    def reuse(self) -> None:
+        self.full = None
+
+    def _build_views(self):
+        quad = self.f[:12].view(4, 3, self.n).transpose(1, 2).unbind(0)  # position, velocity, attitude, rates
+        # every tensor a step hands out without expanding: reward, done, the command, the quadcopter observation
+        self._views = (self.f[LR_REWARD], self.b[FB_DONE].view(torch.bool), self.act.T) + quad
+
+    def observation(self, source) -> LazyObservation:
+        v = self._handed_out()
+        return LazyObservation({"position": v[3], "velocity": v[4], "attitude": v[5], "angular_velocity": v[6]},
+                               self, source)
+
+    def step_result(self, source, with_action: bool = False):
+        """Frame.step_result of a lean step: reward, done, info["action"] and
+        obs["quadcopter"] are this frame's views; the rest is lazy."""
+        obs = self.observation(source)
+        v = self._views
+        return obs, v[0], v[1], LazyInfo(self, source, v[2] if with_action else None)
+
+
+class LeanSource:
+    """What materialising a lean frame needs besides the frame: the env's
+    parameters and episode constants as of its last reset (kept alive here
+    for observations that outlive the env's next reset) and its time table.
+    `frame_of(lean)` is the frame's full Frame, expanded once
+    (qt_lean_expand) and then kept on the lean frame; `count[0]` counts the
+    launches."""
+
+    __slots__ = ("env_ref", "batch_ref", "keep", "table", "device", "count")
+
+    def __init__(self, env_ref, batch_ref, keep, table: TimeTable, device, count: list):
+        self.env_ref, self.batch_ref, self.keep = env_ref, batch_ref, keep
+        self.table, self.device, self.count = table, device, count
+
+    def frame_of(self, lean: LeanFrame) -> Frame:
+        fr = lean.full
+        if fr is None:
+            fr = Frame(lean.n, self.device)
+            tab, dev = self.table, self.device
+            with on_device(dev):
+                check(_abi.load().qt_lean_expand(self.env_ref, self.batch_ref, tab.ptr, tab.len, lean.ptr, fr.ptr,
+                                                 raw_stream(dev)), "qt_lean_expand")
+            self.count[0] += 1
+            lean.full = fr.seal()
+        return fr
+
+
 class FramePool:
     """The frames an env's steps write (BatchedQuadcopterEnv): `take(cur)`
     returns a frame that nothing outside the pool holds — neither the Frame
     object (e.g. `env.frame`, `obs.frame`) nor any tensor it handed out
     (Frame.recyclable) — other than `cur`, the frame the step reads; else a
     new one.  The pool keeps `size` frames and forgets the oldest held one
-    past that (its holder owns it)."""
+    past that (its holder owns it).  `kind`: the frame layout (default Frame;
+    LeanFrame for a lean env)."""
 
-    def __init__(self, n: int, device, size: int = 3):
-        self.n, self.device, self.size = n, device, size
-        self.frames: list[Frame] = []
+    def __init__(self, n: int, device, size: int = 3, kind=None):
+        self.n, self.device, self.size, self.kind = n, device, size, kind
+        self.frames: list[_Block] = []
 
     @staticmethod
     def _own_refs(items) -> int:
@@ -230,8 +473,9 @@ class FramePool:
         own = FramePool._OWN
         for fr in self.frames:
             if fr is not cur and sys.getrefcount(fr) == own and fr.recyclable():
+                fr.reuse()
                 return fr
-        fr = Frame(self.n, self.device)
+        fr = (self.kind or Frame)(self.n, self.device)
         if len(self.frames) >= self.size:
             self.frames.remove(next(f for f in self.frames if f is not cur))
         self.frames.append(fr)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Throughput of the per-step API (include/quadtrack.h ABI 9): a Python loop
+"""Throughput of the per-step API (include/quadtrack.h ABI 9; --lean: the lean frames of ABI 10): a Python loop
 of `env.step(ctl.compute_action(obs))` (two launches per step) or
 `env.step_closed(ctl)` (one launch per step) over n episodes, the way the
 reference's Evaluator drives its plugins (eval.py:119-165).
@@ -32,11 +32,22 @@ from quadtrack.controllers import BatchedRiccatiLQR  # noqa: E402
 # per-episode constants: the pattern draw, 3 doubles for linear / sinusoidal,
 # 1 for circular, 0 stationary / figure-8)
 FRAME_OUT = 25 * 8 + 3 * 8 + 5  # the frame a step writes
+LEAN_OUT = 13 * 8 + 3 * 4 + 5  # the lean frame a step writes (QT_LEAN_BYTES: state, reward, int32 counters, flags)
 
 
-def contract_bytes(mode: str, lqi: bool, pattern_doubles: int, freeze: bool) -> dict:
+def contract_bytes(mode: str, lqi: bool, pattern_doubles: int, freeze: bool, lean: bool = False) -> dict:
     integ = 2 * 3 * 8 if lqi else 0
     pat = 8 * pattern_doubles
+    if lean:
+        # lean frames (ABI 10): no time and no target rows are read (the time table is shared by every
+        # episode and stays in cache), the counters are int32
+        step_in = 12 * 8 + 3 * 4 + (1 if freeze else 0)  # x, counters, done flag
+        if mode == "closed":
+            return {"closed_step": step_in + integ + pat + LEAN_OUT + 4 * 8}  # writes lean frame + action
+        # the two-call loop expands every step's frame for the controller's observation
+        expand = 13 * 8 + 3 * 4 + 5 + pat + FRAME_OUT
+        return {"lean_expand": expand, "compute_action": 12 * 8 + integ + 4 * 8,
+                "lean_step": step_in + 4 * 8 + pat + LEAN_OUT}
     step_in = 12 * 8 + 8 + 3 * 8 + (1 if freeze else 0)  # x, t, counters, done flag
     if mode == "closed":
         k = step_in + 6 * 8 + integ + pat + FRAME_OUT + 4 * 8  # + target p, v; writes frame + action
@@ -46,11 +57,11 @@ def contract_bytes(mode: str, lqi: bool, pattern_doubles: int, freeze: bool) -> 
     return {"compute_action": act, "frame_step": step}
 
 
-def run(n, steps, mode, lqi, motion, warm):
+def run(n, steps, mode, lqi, motion, warm, lean=False):
     dev = torch.device("cuda", 0)
     cfg = {"target": {"motion_type": motion}}
     ctl = BatchedRiccatiLQR({"dt": 0.01, "use_lqi": lqi, "q_int": [1e-3, 1e-3, 1e-2]} if lqi else {"dt": 0.01})
-    env = quadtrack.BatchedQuadcopterEnv(n, cfg)
+    env = quadtrack.BatchedQuadcopterEnv(n, cfg, lean=lean)
 
     def loop(k):
         ctl.reset(n)
@@ -70,11 +81,12 @@ def run(n, steps, mode, lqi, motion, warm):
     loop(warm)
     wall, issue, done = loop(steps)
     pat = {"linear": 3, "sinusoidal": 3, "circular": 1}.get(motion, 0)
-    by = contract_bytes(mode, lqi, pat, True)
+    by = contract_bytes(mode, lqi, pat, True, lean)
     per_step = sum(by.values())
     rate = n * steps / wall
-    return {"n": n, "steps": steps, "mode": mode, "controller": "lqi" if lqi else "lqr", "motion": motion,
-            "launches_per_step": 1 if mode == "closed" else 2, "wall_s": wall,
+    return {"n": n, "steps": steps, "mode": mode, "lean": lean, "expand_launches": env.expand_launches,
+            "controller": "lqi" if lqi else "lqr", "motion": motion,
+            "launches_per_step": 1 if mode == "closed" else (3 if lean else 2), "wall_s": wall,
             "env_steps_per_s": rate, "ms_per_step": wall / steps * 1e3, "host_us_per_step": issue / steps * 1e6,
             "contract_bytes_per_env_step": by, "contract_GBps": rate * per_step / 1e9,
             "contract_hbm_frac": rate * per_step / 8e12, "all_done": bool(done.all())}
@@ -88,11 +100,12 @@ def main():
     ap.add_argument("--mode", nargs="+", default=["closed", "two_call"])
     ap.add_argument("--ctl", nargs="+", default=["lqr"])
     ap.add_argument("--motion", default="linear")
+    ap.add_argument("--lean", action="store_true", help="lean frames (BatchedQuadcopterEnv(lean=True), ABI 10)")
     a = ap.parse_args()
     for n in a.n:
         for mode in a.mode:
             for c in a.ctl:
-                print(json.dumps(run(n, a.steps, mode, c == "lqi", a.motion, a.warm)), flush=True)
+                print(json.dumps(run(n, a.steps, mode, c == "lqi", a.motion, a.warm, a.lean)), flush=True)
 
 
 if __name__ == "__main__":
