@@ -546,6 +546,81 @@ int qt_summary_parts(int64_t n, const double* met, double mu_ratio, double mu_er
 int qt_summary_numpy(int64_t n, const double* met, int32_t pass, double mu_ratio, double mu_err, double* out,
                      void* stream);
 
+/* ---- the deep tracking policy (additive: QT_ABI_VERSION is unchanged, --------
+   feature detection goes through qt_policy_version) --------------------------
+   DeepTrackingPolicy (controllers/deep_tracking_policy.py): an f32 MLP on 18
+   features, Linear + activation per hidden layer, Linear(., 4), and
+   sigmoid(raw) * (hi - lo) + lo per output.  All arithmetic is exact f32 on
+   the f32-input MFMA; an output neuron's summation order is fixed
+   (csrc/qt_policy.hpp) and independent of lane, batch size and entry point,
+   so qt_policy_action and qt_policy_rollout give the same command bit for
+   bit on the same observation. */
+
+/* PolicyNetwork._get_activation (deep_tracking_policy.py:94-104) */
+enum qt_activation {
+  QT_ACT_RELU = 0,
+  QT_ACT_TANH = 1,
+  QT_ACT_ELU = 2,
+  QT_ACT_LEAKY_RELU = 3   /* nn.LeakyReLU(0.1) */
+};
+
+#define QT_POLICY_MAX_HIDDEN 4
+#define QT_POLICY_MAX_WIDTH 128
+#define QT_POLICY_INPUTS 18
+
+/* The network.  `params` is a DEVICE block of QT_POLICY_BLOCK_FLOATS(n_hidden,
+   NT) floats in the kernels' operand order, with NT = the number of 32-row
+   tiles of the widest hidden layer rounded up to 1, 2 or 4 and HP = 32 NT
+   (rows and columns beyond a layer's size are zero):
+     layer 0:            A[NT][9][64], A[mt][s][l] = W0[32 mt + (l & 31)][2 s + (l >> 5)]; bias[HP]
+     layer 1..n_hidden-1: A[NT][NT][16][64], A[mt][kt][r][l] =
+                         W[32 mt + (l & 31)][32 kt + 8 (r >> 2) + 4 (l >> 5) + (r & 3)]; bias[HP]
+     output layer:       W[4][HP] row-major; bias[4]
+   where W is nn.Linear's weight [out][in] (quadtrack.policy.pack_params builds
+   the block from a state dict).  Networks beyond 4 hidden layers or 128 units
+   per layer are rejected (QT_EINVAL). */
+typedef struct qt_policy {
+  int32_t n_hidden;       /* 1..QT_POLICY_MAX_HIDDEN */
+  int32_t width[4];       /* 1..QT_POLICY_MAX_WIDTH each (the first n_hidden used) */
+  int32_t activation;     /* enum qt_activation */
+  int32_t pad_;
+  const float* params;    /* device, layout above */
+  double lo[4], hi[4];    /* output_bounds: thrust, roll, pitch, yaw rate */
+} qt_policy;
+#define QT_POLICY_BLOCK_FLOATS(nh, nt) \
+  ((int64_t)(nt) * 576 + 32 * (nt) + (int64_t)((nh) - 1) * ((int64_t)(nt) * (nt) * 1024 + 32 * (nt)) + 128 * (nt) + 4)
+
+/* The observation the policy reads (DeepTrackingPolicy._extract_features,
+   deep_tracking_policy.py:241-286): quadcopter position, velocity, attitude,
+   angular velocity and target position, velocity, [3][n] views each.  (The
+   classical controllers' qt_obs_view carries neither attitude nor rates.) */
+typedef struct qt_policy_obs {
+  qt_view pos, vel, att, rate, tpos, tvel;
+} qt_policy_obs;
+
+/* 1: this library has the policy entry points below. */
+int qt_policy_version(void);
+
+/* DeepTrackingPolicy.compute_action for a batch of observations: action[4][n]
+   (thrust, roll, pitch, yaw rate; f32 results widened to FP64).  frozen[n]
+   (may be NULL): episodes with a nonzero entry get a zero action row, as the
+   closed-loop step entry points give a done episode under freeze_done. */
+int qt_policy_action(const qt_policy* policy, int64_t n, const qt_policy_obs* obs, const int8_t* frozen,
+                     double* action, void* stream);
+
+/* The fused closed loop with the policy as the controller: per step the
+   policy's forward pass on the current observation, then the exact env step
+   and the Evaluator's metric accumulators, as qt_rollout's exact flavour
+   (action parsing, closed-form RK4 / Euler, constraints, termination, pre-step
+   error and effort accumulators, violations).  The control effort is that of
+   the policy's own command (before the env clips it).  Done episodes stay
+   frozen; may be called in chunks.  rec as qt_rollout (rows 12-15: the
+   policy's command).  batch->motion / pattern / plant_mass per episode;
+   batch->order must be NULL; batch->K and the other controller fields are not
+   read (K may be NULL); st.integ is not touched. */
+int qt_policy_rollout(const qt_env_params* env, const qt_policy* policy, const qt_criteria* crit,
+                      const qt_batch* batch, qt_state st, int32_t nsteps, double* rec, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,9 +12,11 @@ a visible GPU the numeric calls raise.
 from . import _abi
 from .controllers import (
     BaseController,
+    BatchedDeepPolicy,
     BatchedLQR,
     BatchedPID,
     BatchedRiccatiLQR,
+    DeepTrackingPolicy,
     LQRController,
     PIDController,
     RiccatiLQRController,
@@ -23,6 +25,7 @@ from .controllers import (
 )
 from .env import BatchedQuadcopterEnv, EnvConfig, QuadcopterEnv, TargetMotion
 from .eval import BatchedEvaluator, Evaluator, evaluate_batched, load_controller, run_hyperparameter_sweep
+from .policy import evaluate_policy, run_policy_loop
 from .rollout import RolloutResult, run_closed_loop
 from .utils import EpisodeMetrics, EvaluationSummary, SuccessCriteria, compute_episode_metrics
 
@@ -32,4 +35,5 @@ __all__ = ["BaseController", "BatchedLQR", "BatchedPID", "BatchedRiccatiLQR", "L
            "RiccatiLQRController", "batched_controller", "solve_dare",
            "BatchedQuadcopterEnv", "EnvConfig", "QuadcopterEnv", "TargetMotion", "Evaluator", "BatchedEvaluator", "evaluate_batched",
            "load_controller", "run_hyperparameter_sweep", "RolloutResult", "run_closed_loop", "EpisodeMetrics", "EvaluationSummary",
-           "SuccessCriteria", "compute_episode_metrics", "_abi"]
+           "SuccessCriteria", "compute_episode_metrics", "_abi", "BatchedDeepPolicy", "DeepTrackingPolicy",
+           "run_policy_loop", "evaluate_policy"]

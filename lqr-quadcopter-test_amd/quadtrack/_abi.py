@@ -91,6 +91,30 @@ class ObsView(C.Structure):
     _fields_ = [(k, View) for k in ("pos", "vel", "tpos", "tvel", "tacc", "time")]
 
 
+class Policy(C.Structure):
+    """qt_policy (the deep tracking policy; additive to ABI 10)"""
+
+    _fields_ = [("n_hidden", C.c_int32), ("width", C.c_int32 * 4), ("activation", C.c_int32), ("pad_", C.c_int32),
+                ("params", C.c_void_p), ("lo", C.c_double * 4), ("hi", C.c_double * 4)]
+
+
+class PolicyObs(C.Structure):
+    """qt_policy_obs"""
+
+    _fields_ = [(k, View) for k in ("pos", "vel", "att", "rate", "tpos", "tvel")]
+
+
+# enum qt_activation, limits of qt_policy
+ACTIVATIONS = ("relu", "tanh", "elu", "leaky_relu")
+POLICY_MAX_HIDDEN, POLICY_MAX_WIDTH, POLICY_INPUTS = 4, 128, 18
+POLICY_VERSION = 1
+
+
+def policy_block_floats(n_hidden: int, nt: int) -> int:
+    """QT_POLICY_BLOCK_FLOATS(n_hidden, nt)"""
+    return nt * 576 + 32 * nt + (n_hidden - 1) * (nt * nt * 1024 + 32 * nt) + 128 * nt + 4
+
+
 # observation frame (qt_frame_row / qt_frame_count / qt_frame_flag, ABI 9)
 FR_ROWS, FC_ROWS, FB_ROWS = 25, 3, 5
 FR_X, FR_TARGET, FR_TIME, FR_ERR, FR_REWARD, FR_RATIO = 0, 12, 21, 22, 23, 24
@@ -118,7 +142,7 @@ EXPORTS = ("qt_abi_version", "qt_host_alloc", "qt_host_free", "qt_stream_sync", 
            "qt_episode_metrics", "qt_metrics_from_arrays", "qt_dare_batched", "qt_dare_dense", "qt_summary",
            "qt_summary_parts", "qt_summary_numpy", "qt_stream_uniform", "qt_frame_reset", "qt_frame_step",
            "qt_compute_action_obs", "qt_frame_closed_step", "qt_lean_reset", "qt_lean_closed_step", "qt_lean_step",
-           "qt_lean_expand")
+           "qt_lean_expand", "qt_policy_version", "qt_policy_action", "qt_policy_rollout")
 
 _lib = None
 
@@ -169,6 +193,9 @@ def load():
     L.qt_lean_closed_step.argtypes = [P(EnvParams), P(CtrlParams), P(Batch), vp, i64, i64, vp, vp, vp, vp, i32, vp]
     L.qt_lean_step.argtypes = [P(EnvParams), P(Batch), vp, i64, i64, vp, View, vp, i32, vp]
     L.qt_lean_expand.argtypes = [P(EnvParams), P(Batch), vp, i64, vp, vp, vp]
+    L.qt_policy_version.argtypes = []
+    L.qt_policy_action.argtypes = [P(Policy), i64, P(PolicyObs), vp, vp, vp]
+    L.qt_policy_rollout.argtypes = [P(EnvParams), P(Policy), P(Criteria), P(Batch), State, i32, vp, vp]
     for name in EXPORTS[1:]:
         getattr(L, name).restype = C.c_int
     v = L.qt_abi_version()

@@ -1,0 +1,334 @@
+"""Deep tracking policy — inference drop-in for the reference's
+`controllers/deep_tracking_policy.py` on the HIP kernels of csrc/qt_policy.hip.
+
+`DeepTrackingPolicy` mirrors the reference class for one episode;
+`BatchedDeepPolicy` holds the weights as one f32 device block in the kernels'
+operand order (`pack_params`, include/quadtrack.h `qt_policy`) and evaluates
+n observations per launch (`qt_policy_action`) or runs the fused closed loop
+(`qt_policy_rollout`, through `quadtrack.policy.run_policy_loop`).  Every
+forward pass runs on the GPU in exact f32; there is no eager fallback.
+"""
+
+from __future__ import annotations
+
+import ctypes as C
+from pathlib import Path
+
+import numpy as np
+import torch
+
+from .. import _abi
+from .._abi import ACTIVATIONS, POLICY_INPUTS, POLICY_MAX_HIDDEN, POLICY_MAX_WIDTH, Policy, PolicyObs, check, on_device
+from .._abi import raw_stream
+from .base import BaseController
+
+F64 = torch.float64
+
+DEFAULT_OUTPUT_BOUNDS = {"thrust": (0.0, 20.0), "roll_rate": (-3.0, 3.0), "pitch_rate": (-3.0, 3.0),
+                         "yaw_rate": (-3.0, 3.0)}
+BOUND_KEYS = ("thrust", "roll_rate", "pitch_rate", "yaw_rate")
+
+
+def validate_architecture(hidden_sizes, activation: str) -> list[int]:
+    """The sizes the kernels accept: 1..4 hidden layers of 1..128 units, one of
+    the reference's activations (PolicyNetwork._get_activation's message)."""
+    if activation not in ACTIVATIONS:
+        raise ValueError(f"Unknown activation: {activation}. Valid: {list(ACTIVATIONS)}")
+    sizes = [int(h) for h in hidden_sizes]
+    if not 1 <= len(sizes) <= POLICY_MAX_HIDDEN:
+        raise ValueError(f"hidden_sizes must list 1..{POLICY_MAX_HIDDEN} layers, got {len(sizes)}")
+    for h in sizes:
+        if not 1 <= h <= POLICY_MAX_WIDTH:
+            raise ValueError(f"hidden layer widths must be in 1..{POLICY_MAX_WIDTH}, got {h}")
+    return sizes
+
+
+def policy_tiles(hidden_sizes) -> int:
+    """NT of the packed block: 32-row tiles of the widest layer, rounded up to 1, 2 or 4."""
+    t = (max(hidden_sizes) + 31) // 32
+    return 4 if t == 3 else t
+
+
+def _crow(r: int, half: int) -> int:
+    """Row of accumulator register r in lane half `half` of a 32x32 MFMA tile."""
+    return 8 * (r >> 2) + 4 * half + (r & 3)
+
+
+def layer_names(n_hidden: int) -> list[str]:
+    """State-dict prefixes in layer order (the reference's Sequential puts an
+    activation module after every Linear: indices 0, 2, 4, ...)."""
+    return [f"feature_extractor.{2 * i}" for i in range(n_hidden)] + ["output_layer"]
+
+
+def pack_params(state_dict, hidden_sizes) -> np.ndarray:
+    """The qt_policy parameter block (float32, include/quadtrack.h) of a
+    reference-format state dict: every layer's weight in the MFMA A-operand
+    order of csrc/qt_policy.hpp, zero-padded to HP = 32 NT rows / columns."""
+    sizes = [int(h) for h in hidden_sizes]
+    nh, nt = len(sizes), policy_tiles(sizes)
+    hp = 32 * nt
+    W, B = [], []
+    dims = [POLICY_INPUTS] + sizes + [4]
+    for i, name in enumerate(layer_names(nh)):
+        w = np.asarray(state_dict[f"{name}.weight"].detach().cpu() if isinstance(state_dict[f"{name}.weight"], torch.Tensor)
+                       else state_dict[f"{name}.weight"], dtype=np.float32)
+        b = np.asarray(state_dict[f"{name}.bias"].detach().cpu() if isinstance(state_dict[f"{name}.bias"], torch.Tensor)
+                       else state_dict[f"{name}.bias"], dtype=np.float32)
+        if w.shape != (dims[i + 1], dims[i]) or b.shape != (dims[i + 1],):
+            raise ValueError(f"{name}: expected weight {(dims[i + 1], dims[i])} and bias {(dims[i + 1],)}, "
+                             f"got {w.shape} and {b.shape}")
+        W.append(w)
+        B.append(b)
+    lane = np.arange(64)
+    row, half = lane & 31, lane >> 5
+    parts = []
+    # layer 0: A[mt][s][l] = W0[32 mt + (l & 31)][2 s + (l >> 5)]
+    w0 = np.zeros((hp, POLICY_INPUTS), np.float32)
+    w0[:sizes[0]] = W[0]
+    a0 = np.empty((nt, 9, 64), np.float32)
+    for mt in range(nt):
+        for s in range(9):
+            a0[mt, s] = w0[32 * mt + row, 2 * s + half]
+    parts += [a0.ravel(), _padded(B[0], hp)]
+    # hidden layers: A[mt][kt][r][l] = W[32 mt + (l & 31)][32 kt + crow(r, l >> 5)]
+    for i in range(1, nh):
+        w = np.zeros((hp, hp), np.float32)
+        w[:sizes[i], :sizes[i - 1]] = W[i]
+        a = np.empty((nt, nt, 16, 64), np.float32)
+        for mt in range(nt):
+            for kt in range(nt):
+                for r in range(16):
+                    a[mt, kt, r] = w[32 * mt + row, 32 * kt + _crow(r, 0) + 4 * half]
+        parts += [a.ravel(), _padded(B[i], hp)]
+    wo = np.zeros((4, hp), np.float32)
+    wo[:, :sizes[-1]] = W[nh]
+    parts += [wo.ravel(), B[nh]]
+    block = np.concatenate(parts).astype(np.float32)
+    assert block.size == _abi.policy_block_floats(nh, nt)
+    return block
+
+
+def _padded(v: np.ndarray, n: int) -> np.ndarray:
+    out = np.zeros(n, np.float32)
+    out[:v.size] = v
+    return out
+
+
+def extract_features(observation: dict) -> np.ndarray:
+    """DeepTrackingPolicy._extract_features on the host (deep_tracking_policy.py:241-286):
+    [target - quad position, target - quad velocity, attitude, angular
+    velocity, target position, target velocity], float64 then float32.  The
+    kernels form the same 18 numbers per episode; this is for callers that
+    want to look at them."""
+    quad, target = observation["quadcopter"], observation["target"]
+    tp, tv = np.array(target["position"]), np.array(target["velocity"])
+    return np.concatenate([tp - np.array(quad["position"]), tv - np.array(quad["velocity"]),
+                           np.array(quad["attitude"]), np.array(quad["angular_velocity"]), tp, tv]).astype(np.float32)
+
+
+def policy_obs_view(obs, n: int, device):
+    """qt_policy_obs of an observation dict of [n, 3] float64 tensors on `device` (any strides)."""
+    from ..step import tensor_view
+
+    q, tg = obs["quadcopter"], obs["target"]
+    v = PolicyObs()
+    v.pos = tensor_view(q["position"], 3, n, "position", device)
+    v.vel = tensor_view(q["velocity"], 3, n, "velocity", device)
+    v.att = tensor_view(q["attitude"], 3, n, "attitude", device)
+    v.rate = tensor_view(q["angular_velocity"], 3, n, "angular velocity", device)
+    v.tpos = tensor_view(tg["position"], 3, n, "target position", device)
+    v.tvel = tensor_view(tg["velocity"], 3, n, "target velocity", device)
+    return v
+
+
+def _bounds(output_bounds):
+    ob = dict(DEFAULT_OUTPUT_BOUNDS if output_bounds is None else output_bounds)
+    lo = [float(ob[k][0]) for k in BOUND_KEYS]
+    hi = [float(ob[k][1]) for k in BOUND_KEYS]
+    return ob, lo, hi
+
+
+class BatchedDeepPolicy:
+    """The policy for n episodes at once: weights in one f32 device block.
+
+    compute_action(obs) -> [n, 4] float64 tensor (thrust, roll, pitch, yaw
+    rate), usable with BatchedQuadcopterEnv.step; BatchedQuadcopterEnv.step_closed
+    accepts the policy itself.  reset(n) is a no-op (a feed-forward network
+    has no state)."""
+
+    def __init__(self, state_dict, hidden_sizes=(64, 64), activation: str = "relu", output_bounds=None, device=None):
+        self.hidden_sizes = validate_architecture(hidden_sizes, activation)
+        self.activation = activation
+        self.output_bounds, lo, hi = _bounds(output_bounds)
+        block = pack_params(state_dict, self.hidden_sizes)
+        self.device = _abi.require_gpu(device)
+        self.params = torch.as_tensor(block, device=self.device)
+        p = Policy()
+        p.n_hidden = len(self.hidden_sizes)
+        for i, h in enumerate(self.hidden_sizes):
+            p.width[i] = h
+        p.activation = ACTIVATIONS.index(activation)
+        p.params = self.params.data_ptr()
+        for i in range(4):
+            p.lo[i], p.hi[i] = lo[i], hi[i]
+        self.c_policy = p
+        self._ref = C.byref(p)
+        lib = _abi.load()
+        if lib.qt_policy_version() != _abi.POLICY_VERSION:
+            raise ImportError("libquadtrack has another policy ABI than this package")
+
+    @classmethod
+    def from_state_dict(cls, state_dict, hidden_sizes=(64, 64), activation: str = "relu", output_bounds=None,
+                        device=None) -> "BatchedDeepPolicy":
+        return cls(state_dict, hidden_sizes, activation, output_bounds, device)
+
+    @classmethod
+    def from_checkpoint(cls, path, device=None) -> "BatchedDeepPolicy":
+        """From a reference-format checkpoint file (DeepTrackingPolicy.save_checkpoint)."""
+        ck = load_checkpoint_file(path)
+        return cls(ck["model_state_dict"], ck["hidden_sizes"], ck.get("activation", "relu"), ck.get("output_bounds"),
+                   device)
+
+    def reset(self, n: int | None = None) -> None:
+        pass
+
+    def compute_action(self, obs, frozen: torch.Tensor | None = None) -> torch.Tensor:
+        """Actions [n, 4] for an observation dict of [n, 3] float64 tensors on
+        the policy's device (BatchedQuadcopterEnv's observation, or any
+        strides).  frozen: optional [n] int8 / bool tensor; its nonzero
+        episodes get a zero action row."""
+        n = obs["quadcopter"]["position"].shape[0]
+        v = policy_obs_view(obs, n, self.device)
+        if frozen is not None and (frozen.device != self.device or frozen.numel() != n or frozen.element_size() != 1
+                                   or not frozen.is_contiguous()):
+            raise ValueError(f"frozen must be a contiguous one-byte [{n}] tensor on {self.device}")
+        out = torch.empty(4, n, dtype=F64, device=self.device)
+        with on_device(self.device):
+            check(_abi.load().qt_policy_action(self._ref, n, C.byref(v), None if frozen is None else frozen.data_ptr(),
+                                               out.data_ptr(), raw_stream(self.device)), "qt_policy_action")
+        return out.T
+
+    def rollout(self, env, crit, batch, st, nsteps: int, rec: torch.Tensor | None = None) -> None:
+        """qt_policy_rollout on a core.EpisodeBatch / core.RolloutState (in place; chunks allowed)."""
+        if batch.order is not None:
+            raise ValueError("the policy rollout runs episodes in index order (order must be None)")
+        if batch.device != self.device:
+            raise ValueError(f"the batch is on {batch.device}, the policy on {self.device}")
+        if rec is not None and (rec.numel() < nsteps * 16 * batch.n or rec.dtype != F64 or not rec.is_contiguous()):
+            raise ValueError("rec must hold nsteps * 16 * n contiguous float64")
+        with torch.cuda.device(self.device):
+            check(_abi.load().qt_policy_rollout(C.byref(env), self._ref, C.byref(crit),
+                                                C.byref(batch.c_batch(with_k=False)), st.c_state(), int(nsteps),
+                                                _abi.ptr(rec), _abi.stream_of(self.device)), "qt_policy_rollout")
+
+
+def load_checkpoint_file(path) -> dict:
+    path = Path(path)
+    if not path.exists():
+        raise FileNotFoundError(f"Checkpoint not found: {path}")
+    # weights_only=False: the reference's checkpoints carry config and metadata dicts
+    return torch.load(path, map_location="cpu", weights_only=False)
+
+
+def _activation_module(name: str) -> torch.nn.Module:
+    return {"relu": torch.nn.ReLU, "tanh": torch.nn.Tanh, "elu": torch.nn.ELU,
+            "leaky_relu": lambda: torch.nn.LeakyReLU(0.1)}[name]()
+
+
+class _Weights(torch.nn.Module):
+    """The reference network's parameter container (same module names, same
+    construction order, so torch.manual_seed gives the reference's weights and
+    state dicts interchange).  It only holds weights: inference runs in the
+    HIP kernels."""
+
+    def __init__(self, hidden_sizes, activation):
+        super().__init__()
+        layers, prev = [], POLICY_INPUTS
+        for h in hidden_sizes:
+            layers += [torch.nn.Linear(prev, h), _activation_module(activation)]
+            prev = h
+        self.feature_extractor = torch.nn.Sequential(*layers)
+        self.output_layer = torch.nn.Linear(prev, 4)
+        for m in self.modules():  # Xavier-uniform weights, zero biases (deep_tracking_policy.py:106-112)
+            if isinstance(m, torch.nn.Linear):
+                torch.nn.init.xavier_uniform_(m.weight)
+                torch.nn.init.zeros_(m.bias)
+        self.input_dim = POLICY_INPUTS
+        self.hidden_sizes = list(hidden_sizes)
+        self.activation_name = activation
+
+
+class DeepTrackingPolicy(BaseController):
+    """Drop-in for the reference's DeepTrackingPolicy (inference).
+
+    config keys: hidden_sizes (default [64, 64]), activation ("relu", "tanh",
+    "elu", "leaky_relu"), output_bounds, checkpoint_path.  Weights are
+    Xavier-uniform with zero biases from torch's generator (torch.manual_seed
+    gives the reference's weights) or come from a reference-format checkpoint.
+    compute_action runs the network on the GPU (qt_policy_action with n = 1).
+
+    Out of scope: to_onnx, train_mode, get_parameters and training as a whole
+    (the weights come from the reference's trainer through a checkpoint)."""
+
+    def __init__(self, config: dict | None = None, device: str | None = None):
+        super().__init__(name="deep_tracking", config=config)
+        config = config or {}
+        if device is None:
+            device = "cuda" if torch.cuda.is_available() else "cpu"
+        self.device = torch.device(device)
+        hidden_sizes = config.get("hidden_sizes", [64, 64])
+        activation = config.get("activation", "relu")
+        validate_architecture(hidden_sizes, activation)
+        self.network = _Weights(list(hidden_sizes), activation)
+        self.network.output_bounds = _bounds(config.get("output_bounds"))[0]
+        self._batched: BatchedDeepPolicy | None = None
+        if config.get("checkpoint_path") is not None:
+            self.load_checkpoint(config["checkpoint_path"])
+
+    def to_batched(self, device=None) -> BatchedDeepPolicy:
+        """The same weights as a BatchedDeepPolicy (a snapshot)."""
+        net = self.network
+        return BatchedDeepPolicy(net.state_dict(), net.hidden_sizes, net.activation_name, net.output_bounds,
+                                 device if device is not None else (self.device if self.device.type == "cuda" else None))
+
+    def compute_action(self, observation: dict) -> dict:
+        if self._batched is None:
+            self._batched = self.to_batched()
+        b = self._batched
+        row = lambda v: torch.as_tensor(np.asarray(v, dtype=np.float64).reshape(1, 3), device=b.device)  # noqa: E731
+        quad, target = observation["quadcopter"], observation["target"]
+        obs = {"quadcopter": {k: row(quad[k]) for k in ("position", "velocity", "attitude", "angular_velocity")},
+               "target": {k: row(target[k]) for k in ("position", "velocity")}}
+        a = b.compute_action(obs)[0].cpu().numpy()
+        return {"thrust": float(a[0]), "roll_rate": float(a[1]), "pitch_rate": float(a[2]), "yaw_rate": float(a[3])}
+
+    def reset(self) -> None:
+        pass
+
+    def save_checkpoint(self, path, metadata: dict | None = None) -> None:
+        """The reference's checkpoint file (deep_tracking_policy.py:304-332)."""
+        path = Path(path)
+        path.parent.mkdir(parents=True, exist_ok=True)
+        net = self.network
+        checkpoint = {"model_state_dict": net.state_dict(), "config": self.config, "input_dim": net.input_dim,
+                      "hidden_sizes": net.hidden_sizes, "activation": net.activation_name,
+                      "output_bounds": net.output_bounds}
+        if metadata:
+            checkpoint["metadata"] = metadata
+        torch.save(checkpoint, path)
+
+    def load_checkpoint(self, path) -> dict:
+        """Load a reference-format checkpoint; returns its metadata
+        (deep_tracking_policy.py:334-373, the same errors)."""
+        checkpoint = load_checkpoint_file(path)
+        net = self.network
+        if checkpoint.get("input_dim") != net.input_dim:
+            raise ValueError(f"Input dim mismatch: checkpoint has {checkpoint.get('input_dim')}, "
+                             f"network has {net.input_dim}")
+        if checkpoint.get("hidden_sizes") != net.hidden_sizes:
+            raise ValueError(f"Hidden sizes mismatch: checkpoint has "
+                             f"{checkpoint.get('hidden_sizes')}, but network is configured "
+                             f"with {net.hidden_sizes}. Cannot load incompatible model.")
+        net.load_state_dict(checkpoint["model_state_dict"])
+        self._batched = None
+        return checkpoint.get("metadata", {})

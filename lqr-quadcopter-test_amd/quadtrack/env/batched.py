@@ -11,7 +11,9 @@ tensors.  Each call is one kernel launch (include/quadtrack.h ABI 9):
                  info, for every episode (quadcopter_env.py:152-293)
   step_closed(controller)
                  qt_frame_closed_step: the controller's compute_action on the
-                 current observation, then the step, in one launch
+                 current observation, then the step, in one launch (a
+                 BatchedDeepPolicy: two launches, qt_policy_action then the step,
+                 and a lean env's expand launch before them)
 
 Every step writes an observation frame (quadtrack.step.Frame); the returned
 observation / reward / done / info tensors are views of it.  No later step
@@ -38,6 +40,7 @@ import torch
 
 from .. import _abi, core
 from .._abi import FB_DONE, FC_STEP, FR_X, MOTIONS, check, on_device, raw_stream
+from ..controllers.deep import BatchedDeepPolicy
 from ..step import Frame, FramePool, LeanFrame, LeanSource, TimeTable, action_tensor
 from . import seeding
 from .config import as_env_config
@@ -204,11 +207,17 @@ class BatchedQuadcopterEnv:
         (qt_frame_closed_step).  Same results as
         `env.step(controller.compute_action(obs))`; info["action"] holds the
         command ([n, 4]).  With freeze_done, a done episode's controller state
-        is not advanced."""
+        is not advanced.  A BatchedDeepPolicy takes two launches instead
+        (qt_policy_action on the observation, then the step), three on a lean
+        env, whose target observation the policy reads and which is therefore
+        expanded first (qt_lean_expand); the results are those of
+        `env.step(policy.compute_action(obs))` bit for bit."""
         fr = self._current()
         n, dev = self.num_envs, self.device
         if controller.device != dev:
             raise ValueError(f"the controller is on {controller.device}, the environment on {dev}")
+        if isinstance(controller, BatchedDeepPolicy):
+            return self._step_policy(fr, controller)
         cb = self._closed_batch(controller)
         integ = controller._state_for(n)
         if self.lean:
@@ -220,6 +229,18 @@ class BatchedQuadcopterEnv:
                 out.ptr, out.act_ptr, int(self.freeze_done), raw_stream(dev)), "qt_frame_closed_step")
         self._frame = out.seal()
         return out.step_result(with_action=True)
+
+    def _step_policy(self, fr, policy):
+        """step_closed with a deep policy: its action launch on the current
+        observation, then the step launch.  With freeze_done a done episode's
+        action row is 0, as the one-launch closed step gives it.  The policy
+        reads the target's position and velocity, which a lean frame does not
+        hold: on a lean env the observation is expanded first (one more launch
+        and the full frame's bytes per step; `expand_launches` counts it)."""
+        a = policy.compute_action(self.observation(), fr.b[FB_DONE] if self.freeze_done else None)
+        obs, reward, done, info = self.step(a)
+        info["action"] = a
+        return obs, reward, done, info
 
     def _lean_step(self, fr: LeanFrame, a: torch.Tensor):
         """step on lean frames (qt_lean_step)."""

@@ -45,6 +45,7 @@ class RolloutResult:
     record: torch.Tensor | None = None  # [steps, 16, n]: state after step + controller command
     env: object = None                  # EnvParams of the run (trajectory re-runs)
     ctrl: object = None                 # CtrlParams of the run
+    policy: object = None               # BatchedDeepPolicy of a policy run (policy.run_policy_loop)
 
     @property
     def n(self) -> int:
@@ -105,7 +106,7 @@ class RolloutResult:
           on_target       [S, m]     bool, error <= the env's target radius
           steps           [m]        executed steps; rows at or beyond them are NaN / False
         """
-        if self.env is None or self.ctrl is None:
+        if self.env is None or (self.ctrl is None and self.policy is None):
             raise ValueError("trajectories need the run's env and controller parameters (run_closed_loop)")
         dev = self.batch.device
         if episodes is None:
@@ -124,7 +125,9 @@ class RolloutResult:
         if m:
             core.reset(env, sub, st)
         x0 = st.x.clone()
-        if S and m:
+        if S and m and self.policy is not None:
+            self.policy.rollout(env, self.criteria, sub, st, S, rec)  # a policy run re-runs the policy rollout
+        elif S and m:
             core.rollout(env, self.ctrl, self.criteria, sub, st, S, rec)
         times = np.concatenate([[0.0], np.cumsum(np.full(S, env.dt))])  # t_0 .. t_S, sequential t += dt
         tg = _targets_at(env, sub, torch.as_tensor(times, dtype=F64, device=dev))  # [S + 1, 9, m]

@@ -1,0 +1,154 @@
+#!/usr/bin/env python
+"""Deep tracking policy: the fused rollout against the per-step baseline.
+
+  python scripts/bench_policy.py [--episodes 65536] [--steps 3000] [--passes 10] [--hidden 64,64] [--out FILE]
+      qt_policy_rollout, a relu network of the --hidden sizes (torch.manual_seed(0)
+      Xavier weights): best pass of --passes by HIP events around the rollout launch
+      (the reset is outside the events).  Reports ms per pass, ns per executed
+      env-step and the fraction of the 157.3 TF f32 peak, counting 2 flops per
+      multiply-add of the unpadded layers ([64, 64]: 2 x 5,504 per env-step).
+
+  python scripts/bench_policy.py --baseline [--episodes 65536] [--steps 300]
+      The only way to run such a policy without the policy kernels:
+      torch.nn.Sequential on the device, the 18 features built with torch
+      ops, BatchedQuadcopterEnv.step, one step at a time; wall time between
+      two synchronisations, best of --passes (default 3).  Imports nothing
+      the policy feature added, so it also runs on a checkout without it.
+
+Each run prints one JSON line and appends it to --out when given.
+"""
+
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, os.path.join(ROOT, "lqr-quadcopter-test_amd"))
+
+
+def flops_per_step(hidden):
+    dims = [18] + list(hidden) + [4]
+    return 2 * sum(a * b for a, b in zip(dims[:-1], dims[1:]))  # [64, 64]: 11,008
+
+
+PEAK_F32 = 157.3e12
+ENV_CFG = {"target": {"motion_type": "circular"}}
+
+
+def network(device, hidden=(64, 64)):
+    torch.manual_seed(0)
+    layers, prev = [], 18
+    for h in hidden:
+        layers += [torch.nn.Linear(prev, h), torch.nn.ReLU()]
+        prev = h
+    layers.append(torch.nn.Linear(prev, 4))
+    for m in layers:
+        if isinstance(m, torch.nn.Linear):
+            torch.nn.init.xavier_uniform_(m.weight)
+            torch.nn.init.zeros_(m.bias)
+    return torch.nn.Sequential(*layers).to(device).eval()
+
+
+def fused(args):
+    import quadtrack
+    from quadtrack import core
+    from quadtrack.env.config import as_env_config
+    from quadtrack.policy import policy_batch
+
+    dev = torch.device("cuda:0")
+    net = network("cpu", args.hidden)
+    sd = {}
+    for i in range(len(args.hidden)):
+        sd[f"feature_extractor.{2 * i}.weight"], sd[f"feature_extractor.{2 * i}.bias"] = net[2 * i].weight, net[2 * i].bias
+    sd["output_layer.weight"], sd["output_layer.bias"] = net[-1].weight, net[-1].bias
+    pol = quadtrack.BatchedDeepPolicy.from_state_dict(sd, args.hidden, "relu", device=dev)
+    cfg = as_env_config(ENV_CFG)
+    env, crit, n = cfg.to_params(), core.criteria(), args.episodes
+    batch = policy_batch(cfg, n, dev, seeds=np.arange(n))
+    st = core.RolloutState.empty(n, dev)
+    times = []
+    for _ in range(args.passes + 1):  # the first pass warms up
+        core.reset(env, batch, st)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        pol.rollout(env, crit, batch, st, args.steps)
+        e1.record()
+        e1.synchronize()
+        times.append(e0.elapsed_time(e1))
+    times = times[1:]
+    env_steps = float(st.acc[quadtrack._abi.ACC_STEPS].sum())
+    best = min(times)
+    flops = flops_per_step(args.hidden)
+    return {"what": "policy_rollout_fused", "network": f"{list(args.hidden)} relu", "episodes": n, "steps": args.steps,
+            "passes": args.passes, "ms_per_pass_best": best, "ms_per_pass_all": [round(t, 3) for t in times],
+            "env_steps_per_pass": env_steps, "ns_per_env_step": best * 1e6 / env_steps,
+            "flops_per_env_step": flops, "fraction_of_f32_peak": env_steps * flops / (best * 1e-3) / PEAK_F32,
+            "timer": "HIP events around the rollout launch"}
+
+
+def baseline(args):
+    import quadtrack
+
+    dev = torch.device("cuda:0")
+    net = network(dev, args.hidden)
+    n = args.episodes
+    env = quadtrack.BatchedQuadcopterEnv(n, ENV_CFG, device=dev)
+    lo = torch.tensor([0.0, -3.0, -3.0, -3.0], dtype=torch.float32, device=dev)
+    scale = torch.tensor([20.0, 6.0, 6.0, 6.0], dtype=torch.float32, device=dev)
+    times = []
+    with torch.no_grad():
+        for _ in range(args.passes + 1):
+            obs = env.reset(np.arange(n))
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(args.steps):
+                q, tg = obs["quadcopter"], obs["target"]
+                f = torch.cat([tg["position"] - q["position"], tg["velocity"] - q["velocity"], q["attitude"],
+                               q["angular_velocity"], tg["position"], tg["velocity"]], dim=1).float()
+                a = (torch.sigmoid(net(f)) * scale + lo).double()
+                obs, _, _, _ = env.step(a)
+            torch.cuda.synchronize()
+            times.append((time.perf_counter() - t0) * 1e3)
+    times = times[1:]
+    best = min(times)
+    env_steps = float(n * args.steps)
+    return {"what": "policy_rollout_baseline", "network": f"{list(args.hidden)} relu", "episodes": n, "steps": args.steps,
+            "passes": args.passes, "ms_per_pass_best": best, "ms_per_pass_all": [round(t, 3) for t in times],
+            "env_steps_per_pass": env_steps, "ns_per_env_step": best * 1e6 / env_steps,
+            "timer": "wall clock between synchronisations",
+            "path": "torch.nn.Sequential + torch feature build + BatchedQuadcopterEnv.step, one step at a time"}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--baseline", action="store_true")
+    ap.add_argument("--episodes", type=int, default=65536)
+    ap.add_argument("--steps", type=int, default=None)
+    ap.add_argument("--passes", type=int, default=None)
+    ap.add_argument("--hidden", default="64,64", help="hidden layer sizes, comma-separated")
+    ap.add_argument("--out", default=None)
+    args = ap.parse_args()
+    args.hidden = [int(v) for v in args.hidden.split(",")]
+    if args.steps is None:
+        args.steps = 300 if args.baseline else 3000
+    if args.passes is None:
+        args.passes = 3 if args.baseline else 10
+    line = baseline(args) if args.baseline else fused(args)
+    line["device"] = torch.cuda.get_device_name(0)
+    text = json.dumps(line)
+    print(text)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "a") as f:
+            f.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()
