@@ -28,6 +28,9 @@
 // then crow(r, 1) (0, 4, 1, 5, 2, 6, 3, 7, 8, 12, ...); output layer: inputs
 // 0, 1, 2, ... (fmaf chain).  Columns of an MFMA are independent, so an
 // episode's result does not depend on the other lanes of its wave.
+// tests/policy_model.py restates this order as a host program and
+// tests/test_gpu_policy_model.py holds the kernels to it: a change of the
+// order changes this paragraph and that model together.
 //
 // MFMA ignores EXEC: every lane of a wave must reach policy_forward (callers
 // keep the lanes of a partial last wave and of finished episodes alive and

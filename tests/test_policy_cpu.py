@@ -18,6 +18,8 @@ import quadtrack
 from quadtrack import _abi
 from quadtrack.controllers import deep
 
+from policy_model import check_pack_layout
+
 HEADER = os.path.join(ROOT, "include", "quadtrack.h")
 FX = np.load(os.path.join(GOLDEN, "deep_policy.npz"))
 META = json.loads(str(FX["meta_json"]))
@@ -91,61 +93,16 @@ def test_ctypes_mirror_qt_policy(tmp_path):
                                            _abi.policy_block_floats(4, 4)]
 
 
-def crow(r, half):
-    return 8 * (r >> 2) + 4 * half + (r & 3)
-
-
 @pytest.mark.parametrize("name", ["n0", "n3", "n4", "n5"])
 def test_pack_params_layout(name):
     """Every element of the packed block, read back through the layout the
-    header documents, is the state dict's weight (or an exact zero of padding)."""
+    header documents, is the state dict's weight (or an exact zero of padding)
+    (the check itself: policy_model.check_pack_layout, shared with the
+    architecture matrix of tests/test_policy_model_cpu.py)."""
     spec, sd = spec_of(name), state_dict_of(name)
     sizes = spec["hidden_sizes"]
-    nh, nt = len(sizes), deep.policy_tiles(sizes)
-    assert nt == {"n0": 2, "n3": 2, "n4": 1, "n5": 4}[name]
-    hp = 32 * nt
-    blk = deep.pack_params(sd, sizes)
-    assert blk.dtype == np.float32 and blk.size == _abi.policy_block_floats(nh, nt)
-    names = deep.layer_names(nh)
-    assert names[-1] == "output_layer" and names[0] == "feature_extractor.0"
-
-    def padded(w, rows, cols):
-        out = np.zeros((rows, cols), np.float32)
-        out[:w.shape[0], :w.shape[1]] = w
-        return out
-
-    lane = np.arange(64)
-    row, half = lane & 31, lane >> 5
-    off = 0
-    w0 = padded(sd[names[0] + ".weight"].numpy(), hp, 18)
-    a0 = blk[off:off + nt * 9 * 64].reshape(nt, 9, 64)
-    for mt in range(nt):
-        for s in range(9):
-            assert np.array_equal(a0[mt, s], w0[32 * mt + row, 2 * s + half])
-    off += nt * 9 * 64
-    b0 = sd[names[0] + ".bias"].numpy()
-    assert np.array_equal(blk[off:off + sizes[0]], b0) and not blk[off + sizes[0]:off + hp].any()
-    off += hp
-    for i in range(1, nh):
-        w = padded(sd[names[i] + ".weight"].numpy(), hp, hp)
-        a = blk[off:off + nt * nt * 1024].reshape(nt, nt, 16, 64)
-        for mt in range(nt):
-            for kt in range(nt):
-                for r in range(16):
-                    cols = 32 * kt + np.where(half == 0, crow(r, 0), crow(r, 1))
-                    assert np.array_equal(a[mt, kt, r], w[32 * mt + row, cols])
-        off += nt * nt * 1024
-        b = sd[names[i] + ".bias"].numpy()
-        assert np.array_equal(blk[off:off + sizes[i]], b) and not blk[off + sizes[i]:off + hp].any()
-        off += hp
-    wo = padded(sd["output_layer.weight"].numpy(), 4, hp)
-    assert np.array_equal(blk[off:off + 4 * hp].reshape(4, hp), wo)
-    off += 4 * hp
-    assert np.array_equal(blk[off:off + 4], sd["output_layer.bias"].numpy())
-    assert off + 4 == blk.size
-    # every real weight appears exactly once: the block's sum of squares is the state dict's
-    total = sum(float((v.double() ** 2).sum()) for v in sd.values())
-    assert float((blk.astype(np.float64) ** 2).sum()) == pytest.approx(total, rel=1e-12)
+    assert deep.policy_tiles(sizes) == {"n0": 2, "n3": 2, "n4": 1, "n5": 4}[name]
+    check_pack_layout(sd, sizes)
 
 
 def test_pack_params_rejects_wrong_shapes():
