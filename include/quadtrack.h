@@ -621,6 +621,50 @@ int qt_policy_action(const qt_policy* policy, int64_t n, const qt_policy_obs* ob
 int qt_policy_rollout(const qt_env_params* env, const qt_policy* policy, const qt_criteria* crit,
                       const qt_batch* batch, qt_state st, int32_t nsteps, double* rec, void* stream);
 
+/* ---- policy populations (additive: QT_ABI_VERSION and qt_policy_version are
+   unchanged, feature detection goes through qt_policy_population_version) ----
+   Many networks of one shape in one fused rollout: member m of the population
+   runs episodes [m E, (m + 1) E) of the batch with its own parameter block at
+   shape.params + m * stride.  State, batch and rec arrays are compact
+   (n = members * episodes_per_member columns).  Launch slots are padded per
+   member to whole waves, EP = 64 ceil(E / 64): slot p belongs to member p / EP
+   with local index p % EP and is live when local < E, so a wave never holds
+   two members.  The dead lanes of a member's last wave reach every MFMA, read
+   a clamped episode of their own member, take no env step and store nothing.
+   Everything else is qt_policy_rollout's episode body (same device functions,
+   same order, same rec rows, same chunking and freeze semantics): a member's
+   results are bit for bit those of qt_policy_rollout on that member alone.
+   When the blocks of a workgroup's four waves fit the CU's LDS (160 KiB: four
+   times the block rounded up to 256 bytes) every wave runs its network from
+   its own LDS copy of its block; larger shapes read global memory.  The
+   environment variable QT_POPULATION_STAGE=0, read at every call, selects the
+   global-memory kernels for every shape (timing comparisons); the results are
+   the same bits.
+   Out of scope: members with different architectures, activations or output
+   bounds; a member per 32-lane tile; a population form of qt_policy_action or
+   of the closed per-step entry points. */
+typedef struct qt_policy_population {
+  qt_policy shape;          /* n_hidden, width, activation, lo / hi shared by all members;
+                               shape.params = member 0's block */
+  int32_t members;          /* M >= 1 */
+  int32_t pad_;
+  int64_t stride;           /* floats between consecutive members' blocks,
+                               >= QT_POLICY_BLOCK_FLOATS(n_hidden, NT) */
+  int64_t episodes_per_member;  /* E >= 1 */
+} qt_policy_population;
+
+/* 1: this library has qt_policy_population_rollout. */
+int qt_policy_population_version(void);
+
+/* qt_policy_rollout for a population (layout above).  QT_EINVAL before any
+   launch: a NULL population or NULL params, an invalid shape (qt_policy's
+   rules), members < 1, episodes_per_member < 1, stride below the block size,
+   batch->n != members * episodes_per_member, batch->order != NULL, or a slot
+   count whose grid does not fit an int.  nsteps == 0 returns QT_OK. */
+int qt_policy_population_rollout(const qt_env_params* env, const qt_policy_population* population,
+                                 const qt_criteria* crit, const qt_batch* batch, qt_state st, int32_t nsteps,
+                                 double* rec, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,8 +25,10 @@ from .controllers import (
 )
 from .env import BatchedQuadcopterEnv, EnvConfig, QuadcopterEnv, TargetMotion
 from .eval import BatchedEvaluator, Evaluator, evaluate_batched, load_controller, run_hyperparameter_sweep
-from .policy import evaluate_policy, run_policy_loop
+from .policy import (PolicyPopulation, PopulationResult, evaluate_policy, evaluate_population, run_policy_loop,
+                     run_policy_population)
 from .rollout import RolloutResult, run_closed_loop
+from .train import SearchResult, search_policy
 from .utils import EpisodeMetrics, EvaluationSummary, SuccessCriteria, compute_episode_metrics
 
 __version__ = "0.1.0"
@@ -36,4 +38,5 @@ __all__ = ["BaseController", "BatchedLQR", "BatchedPID", "BatchedRiccatiLQR", "L
            "BatchedQuadcopterEnv", "EnvConfig", "QuadcopterEnv", "TargetMotion", "Evaluator", "BatchedEvaluator", "evaluate_batched",
            "load_controller", "run_hyperparameter_sweep", "RolloutResult", "run_closed_loop", "EpisodeMetrics", "EvaluationSummary",
            "SuccessCriteria", "compute_episode_metrics", "_abi", "BatchedDeepPolicy", "DeepTrackingPolicy",
-           "run_policy_loop", "evaluate_policy"]
+           "run_policy_loop", "evaluate_policy", "PolicyPopulation", "PopulationResult", "run_policy_population",
+           "evaluate_population", "search_policy", "SearchResult"]

@@ -98,6 +98,13 @@ class Policy(C.Structure):
                 ("params", C.c_void_p), ("lo", C.c_double * 4), ("hi", C.c_double * 4)]
 
 
+class PolicyPopulation(C.Structure):
+    """qt_policy_population (additive; qt_policy_population_version)"""
+
+    _fields_ = [("shape", Policy), ("members", C.c_int32), ("pad_", C.c_int32), ("stride", C.c_int64),
+                ("episodes_per_member", C.c_int64)]
+
+
 class PolicyObs(C.Structure):
     """qt_policy_obs"""
 
@@ -108,6 +115,7 @@ class PolicyObs(C.Structure):
 ACTIVATIONS = ("relu", "tanh", "elu", "leaky_relu")
 POLICY_MAX_HIDDEN, POLICY_MAX_WIDTH, POLICY_INPUTS = 4, 128, 18
 POLICY_VERSION = 1
+POLICY_POPULATION_VERSION = 1
 
 
 def policy_block_floats(n_hidden: int, nt: int) -> int:
@@ -142,7 +150,8 @@ EXPORTS = ("qt_abi_version", "qt_host_alloc", "qt_host_free", "qt_stream_sync", 
            "qt_episode_metrics", "qt_metrics_from_arrays", "qt_dare_batched", "qt_dare_dense", "qt_summary",
            "qt_summary_parts", "qt_summary_numpy", "qt_stream_uniform", "qt_frame_reset", "qt_frame_step",
            "qt_compute_action_obs", "qt_frame_closed_step", "qt_lean_reset", "qt_lean_closed_step", "qt_lean_step",
-           "qt_lean_expand", "qt_policy_version", "qt_policy_action", "qt_policy_rollout")
+           "qt_lean_expand", "qt_policy_version", "qt_policy_action", "qt_policy_rollout",
+           "qt_policy_population_version", "qt_policy_population_rollout")
 
 _lib = None
 
@@ -196,6 +205,9 @@ def load():
     L.qt_policy_version.argtypes = []
     L.qt_policy_action.argtypes = [P(Policy), i64, P(PolicyObs), vp, vp, vp]
     L.qt_policy_rollout.argtypes = [P(EnvParams), P(Policy), P(Criteria), P(Batch), State, i32, vp, vp]
+    L.qt_policy_population_version.argtypes = []
+    L.qt_policy_population_rollout.argtypes = [P(EnvParams), P(PolicyPopulation), P(Criteria), P(Batch), State, i32,
+                                               vp, vp]
     for name in EXPORTS[1:]:
         getattr(L, name).restype = C.c_int
     v = L.qt_abi_version()

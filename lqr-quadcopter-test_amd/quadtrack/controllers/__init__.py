@@ -2,7 +2,7 @@
 the Riccati controller, its heuristic-LQR fallback and the plugin base)."""
 
 from .base import ACTION_KEYS, DEFAULT_ACTION_LIMITS, ActionLimits, BaseController, validate_action
-from .deep import BatchedDeepPolicy, DeepTrackingPolicy
+from .deep import BatchedDeepPolicy, DeepTrackingPolicy, PolicyPopulation
 from .lqr import BatchedLQR, LQRController, heuristic_gains
 from .pid import BatchedPID, PIDController
 from .riccati_lqr import (
@@ -35,5 +35,5 @@ __all__ = [
     "ACTION_KEYS", "DEFAULT_ACTION_LIMITS", "ActionLimits", "BaseController", "validate_action", "LQRController",
     "BatchedLQR", "PIDController", "BatchedPID", "batched_controller", "heuristic_gains", "BatchedRiccatiLQR",
     "RiccatiLQRController", "build_augmented_lqi_system", "build_linearized_system", "solve_dare",
-    "VALID_CONTROLLER_TYPES", "BatchedDeepPolicy", "DeepTrackingPolicy",
+    "VALID_CONTROLLER_TYPES", "BatchedDeepPolicy", "DeepTrackingPolicy", "PolicyPopulation",
 ]

@@ -158,11 +158,26 @@ class BatchedDeepPolicy:
 
     def __init__(self, state_dict, hidden_sizes=(64, 64), activation: str = "relu", output_bounds=None, device=None):
         self.hidden_sizes = validate_architecture(hidden_sizes, activation)
-        self.activation = activation
-        self.output_bounds, lo, hi = _bounds(output_bounds)
         block = pack_params(state_dict, self.hidden_sizes)
         self.device = _abi.require_gpu(device)
-        self.params = torch.as_tensor(block, device=self.device)
+        self._bind(torch.as_tensor(block, device=self.device), activation, output_bounds)
+
+    @classmethod
+    def from_block(cls, block: torch.Tensor, hidden_sizes=(64, 64), activation: str = "relu", output_bounds=None):
+        """From a packed f32 device block (pack_params' layout), which the policy keeps as it is."""
+        self = cls.__new__(cls)
+        self.hidden_sizes = validate_architecture(hidden_sizes, activation)
+        want = _abi.policy_block_floats(len(self.hidden_sizes), policy_tiles(self.hidden_sizes))
+        if block.dtype != torch.float32 or block.dim() != 1 or block.numel() != want or not block.is_contiguous():
+            raise ValueError(f"the block must be a contiguous float32 [{want}] tensor")
+        self.device = _abi.require_gpu(block.device)
+        self._bind(block, activation, output_bounds)
+        return self
+
+    def _bind(self, block: torch.Tensor, activation: str, output_bounds) -> None:
+        self.activation = activation
+        self.output_bounds, lo, hi = _bounds(output_bounds)
+        self.params = block
         p = Policy()
         p.n_hidden = len(self.hidden_sizes)
         for i, h in enumerate(self.hidden_sizes):
@@ -332,3 +347,208 @@ class DeepTrackingPolicy(BaseController):
         net.load_state_dict(checkpoint["model_state_dict"])
         self._batched = None
         return checkpoint.get("metadata", {})
+
+
+# ------------------------------------------------------------------ populations
+
+PAD = -1  # pack_index's marker of a padding zero
+
+
+def flat_size(hidden_sizes) -> int:
+    """Parameters of the network: the length of parameters_to_vector(network.parameters())."""
+    dims = [POLICY_INPUTS] + [int(h) for h in hidden_sizes] + [4]
+    return sum(dims[i + 1] * dims[i] + dims[i + 1] for i in range(len(dims) - 1))
+
+
+def unflatten(theta, hidden_sizes) -> dict:
+    """The reference-format state dict of a flat parameter vector in
+    parameters_to_vector(network.parameters()) order: per layer the weight
+    [out][in] row-major, then the bias."""
+    sizes = [int(h) for h in hidden_sizes]
+    theta = torch.as_tensor(theta).detach().reshape(-1)
+    if theta.numel() != flat_size(sizes):
+        raise ValueError(f"a {sizes} network has {flat_size(sizes)} parameters, got {theta.numel()}")
+    dims = [POLICY_INPUTS] + sizes + [4]
+    sd, off = {}, 0
+    for i, name in enumerate(layer_names(len(sizes))):
+        o, k = dims[i + 1], dims[i]
+        sd[f"{name}.weight"] = theta[off:off + o * k].reshape(o, k)
+        sd[f"{name}.bias"] = theta[off + o * k:off + o * k + o]
+        off += o * k + o
+    return sd
+
+
+_PACK_INDEX: dict = {}
+
+
+def pack_index(hidden_sizes) -> np.ndarray:
+    """int64 [QT_POLICY_BLOCK_FLOATS]: element i of the packed block is element
+    pack_index[i] of the flat parameter vector, or an exact zero of padding
+    where pack_index[i] == PAD.  Built once per shape by sending every
+    parameter's own position through pack_params (positions are far below 2^24,
+    so float32 carries them exactly), and cached (read-only)."""
+    key = tuple(int(h) for h in hidden_sizes)
+    if key not in _PACK_INDEX:
+        sizes = validate_architecture(key, "relu")
+        tagged = unflatten(torch.arange(1, flat_size(sizes) + 1, dtype=torch.float32), sizes)
+        idx = pack_params(tagged, sizes).astype(np.int64) - 1
+        idx.setflags(write=False)
+        _PACK_INDEX[key] = idx
+    return _PACK_INDEX[key]
+
+
+def population_stride(hidden_sizes) -> int:
+    """Floats between two members' blocks: the block rounded up to 256 bytes,
+    so every member's A-operand rows start on the alignment member 0's have."""
+    nb = _abi.policy_block_floats(len(hidden_sizes), policy_tiles(hidden_sizes))
+    return (nb + 63) // 64 * 64
+
+
+def _member_spec(m, activation, output_bounds):
+    """(weights, hidden_sizes, activation, output_bounds) of one member given
+    as a policy or a state dict; weights: a state dict or a packed device block."""
+    if isinstance(m, DeepTrackingPolicy):
+        net = m.network
+        return net.state_dict(), list(net.hidden_sizes), net.activation_name, _bounds(net.output_bounds)[0]
+    if isinstance(m, BatchedDeepPolicy):
+        return m.params, list(m.hidden_sizes), m.activation, m.output_bounds
+    if isinstance(m, dict):
+        nh = len([k for k in m if k.startswith("feature_extractor.") and k.endswith(".weight")])
+        sizes = [int(m[f"feature_extractor.{2 * i}.weight"].shape[0]) for i in range(nh)]
+        return m, sizes, activation, _bounds(output_bounds)[0]
+    raise TypeError(f"a population member is a DeepTrackingPolicy, a BatchedDeepPolicy or a state dict, "
+                    f"not {type(m).__name__}")
+
+
+class PolicyPopulation:
+    """M networks of one shape as one [M, stride] f32 device tensor of packed
+    blocks (qt_policy_population): the fused rollout runs every member on its
+    own episodes in one launch (quadtrack.policy.run_policy_population).
+
+    members   DeepTrackingPolicy / BatchedDeepPolicy / reference-format state
+              dicts; one shape, activation and output bounds (ValueError
+              otherwise).  activation / output_bounds describe state dicts.
+    from_flat(template, theta) builds it from a [M, P] float32 tensor of flat
+    parameter vectors (parameters_to_vector order) with one device gather
+    through pack_index: no host packing in an ask / tell loop."""
+
+    def __init__(self, members, activation: str = "relu", output_bounds=None, device=None):
+        specs = [_member_spec(m, activation, output_bounds) for m in members]
+        if not specs:
+            raise ValueError("a population needs at least one member")
+        _, sizes, act, bounds = specs[0]
+        sizes = validate_architecture(sizes, act)
+        for j, (_, s, a, b) in enumerate(specs[1:], 1):
+            if list(s) != sizes:
+                raise ValueError(f"member {j} has hidden sizes {list(s)}, member 0 has {sizes}")
+            if a != act:
+                raise ValueError(f"member {j} has activation {a}, member 0 has {act}")
+            if _bounds(b)[1:] != _bounds(bounds)[1:]:
+                raise ValueError(f"member {j} has other output bounds than member 0")
+        nb = _abi.policy_block_floats(len(sizes), policy_tiles(sizes))
+        host = [w if isinstance(w, torch.Tensor) else pack_params(w, sizes) for w, *_ in specs]  # checks the shapes
+        dev = _abi.require_gpu(device)
+        blocks = torch.zeros(len(specs), population_stride(sizes), dtype=torch.float32, device=dev)
+        for j, w in enumerate(host):
+            blocks[j, :nb] = w.to(dev) if isinstance(w, torch.Tensor) else torch.as_tensor(w, device=dev)
+        self._bind(blocks, sizes, act, bounds)
+
+    @classmethod
+    def from_flat(cls, template, theta: torch.Tensor, device=None) -> "PolicyPopulation":
+        """template: a DeepTrackingPolicy, a BatchedDeepPolicy or a config
+        dict (shape, activation and bounds; its weights are not read)."""
+        if isinstance(template, dict):
+            sizes, act = list(template.get("hidden_sizes", [64, 64])), template.get("activation", "relu")
+            bounds = _bounds(template.get("output_bounds"))[0]
+        else:
+            _, sizes, act, bounds = _member_spec(template, None, None)
+        sizes = validate_architecture(sizes, act)
+        theta = torch.as_tensor(theta)
+        if theta.dim() != 2 or theta.shape[0] < 1 or theta.shape[1] != flat_size(sizes) or theta.dtype != torch.float32:
+            raise ValueError(f"theta must be a float32 [M, {flat_size(sizes)}] tensor for hidden sizes {sizes}, "
+                             f"got {theta.dtype} {tuple(theta.shape)}")
+        dev = _abi.require_gpu(device if device is not None else (theta.device if theta.is_cuda else None))
+        self = cls.__new__(cls)
+        gather, _ = self._device_index(sizes, dev)
+        src = torch.cat([theta.to(dev), torch.zeros(theta.shape[0], 1, dtype=torch.float32, device=dev)], dim=1)
+        nb = gather.numel()
+        blocks = torch.zeros(theta.shape[0], population_stride(sizes), dtype=torch.float32, device=dev)
+        blocks[:, :nb] = src.index_select(1, gather)
+        self._bind(blocks, sizes, act, bounds)
+        return self
+
+    _INDEX: dict = {}
+
+    @classmethod
+    def _device_index(cls, sizes, dev):
+        """(gather, scatter) on the device, cached per shape: gather maps the
+        block to [theta, 0] columns (padding -> the appended zero), scatter
+        gives every parameter's place in the block."""
+        key = (tuple(sizes), str(dev))
+        if key not in cls._INDEX:
+            idx = pack_index(sizes)
+            real = np.flatnonzero(idx != PAD)
+            scatter = np.empty(flat_size(sizes), np.int64)
+            scatter[idx[real]] = real
+            gather = np.where(idx == PAD, flat_size(sizes), idx)
+            cls._INDEX[key] = (torch.as_tensor(gather, device=dev), torch.as_tensor(scatter, device=dev))
+        return cls._INDEX[key]
+
+    def _bind(self, blocks, sizes, act, bounds) -> None:
+        self.hidden_sizes, self.activation = list(sizes), act
+        self.output_bounds, lo, hi = _bounds(bounds)
+        self.device = blocks.device
+        self.params = blocks
+        self.block_floats = _abi.policy_block_floats(len(sizes), policy_tiles(sizes))
+        c = _abi.PolicyPopulation()
+        p = c.shape
+        p.n_hidden = len(sizes)
+        for i, h in enumerate(sizes):
+            p.width[i] = h
+        p.activation = ACTIVATIONS.index(act)
+        p.params = blocks.data_ptr()
+        for i in range(4):
+            p.lo[i], p.hi[i] = lo[i], hi[i]
+        c.members, c.stride = blocks.shape[0], blocks.shape[1]
+        self.c_population = c
+        if _abi.load().qt_policy_population_version() != _abi.POLICY_POPULATION_VERSION:
+            raise ImportError("libquadtrack has another policy-population ABI than this package")
+
+    @property
+    def members(self) -> int:
+        return self.params.shape[0]
+
+    def __len__(self) -> int:
+        return self.members
+
+    def flat(self) -> torch.Tensor:
+        """[M, P] float32 device tensor of the members' flat parameter vectors (from_flat's inverse)."""
+        _, scatter = self._device_index(self.hidden_sizes, self.device)
+        return self.params.index_select(1, scatter)
+
+    def member(self, m: int) -> BatchedDeepPolicy:
+        """Member m as a BatchedDeepPolicy holding a copy of its block."""
+        if not 0 <= int(m) < self.members:
+            raise IndexError(f"member {m} of a population of {self.members}")
+        return BatchedDeepPolicy.from_block(self.params[int(m), :self.block_floats].clone(), self.hidden_sizes,
+                                            self.activation, self.output_bounds)
+
+    def rollout(self, env, crit, batch, st, nsteps: int, episodes_per_member: int,
+                rec: torch.Tensor | None = None) -> None:
+        """qt_policy_population_rollout on a core.EpisodeBatch / core.RolloutState of
+        members * episodes_per_member episodes (in place; chunks allowed)."""
+        if batch.order is not None:
+            raise ValueError("the policy rollout runs episodes in index order (order must be None)")
+        if batch.device != self.device:
+            raise ValueError(f"the batch is on {batch.device}, the population on {self.device}")
+        if batch.n != self.members * int(episodes_per_member):
+            raise ValueError(f"{batch.n} episodes for {self.members} members x {episodes_per_member}")
+        if rec is not None and (rec.numel() < nsteps * 16 * batch.n or rec.dtype != F64 or not rec.is_contiguous()):
+            raise ValueError("rec must hold nsteps * 16 * n contiguous float64")
+        c = self.c_population
+        c.episodes_per_member = int(episodes_per_member)
+        with torch.cuda.device(self.device):
+            check(_abi.load().qt_policy_population_rollout(C.byref(env), C.byref(c), C.byref(crit),
+                                                           C.byref(batch.c_batch(with_k=False)), st.c_state(),
+                                                           int(nsteps), _abi.ptr(rec), _abi.stream_of(self.device)),
+                  "qt_policy_population_rollout")

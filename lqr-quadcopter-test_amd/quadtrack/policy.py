@@ -5,6 +5,11 @@
 numpy-exact summary, with `qt_policy_rollout` (csrc/qt_policy.hip: the
 policy's f32 forward pass on the MFMA, then the exact env step, per step, in
 one kernel) in place of the classical controllers' rollout.
+
+`run_policy_population` / `evaluate_population` run many networks of one shape
+(`PolicyPopulation`) in one launch, each member on its own episodes
+(`qt_policy_population_rollout`, csrc/qt_policy_population.hip): the batch
+evaluator of gradient-free search (`quadtrack.train.search_policy`).
 """
 
 from __future__ import annotations
@@ -13,13 +18,18 @@ import numpy as np
 import torch
 
 from . import _abi, core
-from .controllers.deep import BatchedDeepPolicy, DeepTrackingPolicy, extract_features, pack_params, policy_tiles
+from dataclasses import dataclass
+
+from .controllers.deep import (BatchedDeepPolicy, DeepTrackingPolicy, PolicyPopulation, extract_features, pack_index,
+                               pack_params, policy_tiles)
+from .env.batched import motion_indices
 from .env.config import as_env_config
 from .rollout import F64, RolloutResult, _criteria, build_batch, max_steps_for
 from .utils.metrics import EvaluationSummary, SuccessCriteria
 
 __all__ = ["BatchedDeepPolicy", "DeepTrackingPolicy", "run_policy_loop", "evaluate_policy", "policy_batch",
-           "pack_params", "policy_tiles", "extract_features"]
+           "pack_params", "policy_tiles", "extract_features", "PolicyPopulation", "PopulationResult", "pack_index",
+           "run_policy_population", "evaluate_population"]
 
 
 class _NoGains:
@@ -105,3 +115,117 @@ def evaluate_policy(policy, env_config=None, num_episodes: int = 10, base_seed: 
     if with_episode_metrics:
         summary.episode_metrics = res.episode_metrics()
     return summary
+
+
+# ------------------------------------------------------------------ populations
+
+@dataclass
+class PopulationResult(RolloutResult):
+    """A population run: n = members * episodes_per_member compact columns,
+    member m owning episodes [m E, (m + 1) E)."""
+
+    population: PolicyPopulation | None = None
+    members: int = 1
+    episodes_per_member: int = 1
+
+    def member_metrics(self) -> torch.Tensor:
+        """The metrics as a [rows, M, E] view."""
+        return self.metrics.view(self.metrics.shape[0], self.members, self.episodes_per_member)
+
+    def member_summary(self, m: int) -> EvaluationSummary:
+        """The numpy-exact EvaluationSummary of member m's episodes: what
+        evaluate_policy gives for that member alone on the same episodes."""
+        from .parallel import reduce_summary
+
+        if not 0 <= int(m) < self.members:
+            raise IndexError(f"member {m} of a population of {self.members}")
+        E = self.episodes_per_member
+        return reduce_summary(self.metrics[:, int(m) * E:(int(m) + 1) * E].contiguous(), self.criteria)
+
+    def fitness(self, kind="tracking_error") -> torch.Tensor:
+        """[M] device tensor, larger is better.  "tracking_error": minus the mean
+        over a member's episodes of mean_tracking_error; "on_target": the mean
+        on_target_ratio; a callable gets member_metrics() and returns [M]."""
+        mm = self.member_metrics()
+        if callable(kind):
+            return kind(mm)
+        if kind == "tracking_error":
+            return -mm[_abi.MET["mean_tracking_error"]].mean(dim=1)
+        if kind == "on_target":
+            return mm[_abi.MET["on_target_ratio"]].mean(dim=1)
+        raise ValueError(f"Unknown fitness: {kind}. Valid: 'tracking_error', 'on_target' or a callable")
+
+    def trajectories(self, episodes=None) -> dict:
+        raise ValueError("a population run keeps no single policy to re-run: use run_policy_loop on "
+                         "population.member(m) for a member's trajectories")
+
+
+def _per_member(values, M: int, E: int, what: str, convert) -> np.ndarray:
+    """An [E] (shared by every member) or [M, E] input as n = M E values, member-major."""
+    if isinstance(values, torch.Tensor):
+        values = values.cpu().numpy()
+    a = np.asarray(values)
+    if a.shape == (M, E):
+        return convert(a.reshape(-1), M * E)
+    if a.shape == (E,):
+        return np.tile(convert(a, E), M)
+    raise ValueError(f"{what} must have shape [{E}] or [{M}, {E}], got {list(a.shape)}")
+
+
+def run_policy_population(population: PolicyPopulation, env_config=None, episodes_per_member: int = 1, seeds=None,
+                          motion=None, plant_mass=None, criteria=None, max_steps: int | None = None,
+                          chunk: int | None = None, record: bool = False) -> PopulationResult:
+    """Every member of the population on its own `episodes_per_member` episodes,
+    in one fused launch (qt_policy_population_rollout): n = M E.
+
+    seeds / motion / plant_mass take shape [E] or [M, E]; an [E] input is
+    shared by every member (common random numbers).  Default seeds: 0..E-1 for
+    each member.  The other arguments are run_policy_loop's.  A member's
+    results are bit for bit those of run_policy_loop on population.member(m)
+    with the same inputs."""
+    if not isinstance(population, PolicyPopulation):
+        raise TypeError(f"expected a PolicyPopulation, got {type(population).__name__}")
+    M, E = population.members, int(episodes_per_member)
+    if E < 1:
+        raise ValueError("episodes_per_member must be >= 1")
+    n = M * E
+    cfg = as_env_config(env_config)
+    env = cfg.to_params()
+    ints = lambda a, k: np.asarray(a, dtype=np.int64).reshape(k)  # noqa: E731
+    seeds = _per_member(np.arange(E) if seeds is None else seeds, M, E, "seeds", ints)
+    if motion is not None:
+        motion = _per_member(motion, M, E, "motion", motion_indices)
+    if plant_mass is not None:
+        plant_mass = _per_member(plant_mass, M, E, "plant_mass", lambda a, k: np.asarray(a, dtype=np.float64).reshape(k))
+    batch = policy_batch(cfg, n, population.device, seeds=seeds, motion=motion, plant_mass=plant_mass)
+    crit = _criteria(criteria)
+    st = core.RolloutState.empty(n, batch.device)
+    core.validate(batch, st)
+    total = max_steps if max_steps is not None else max_steps_for(env)
+    step = chunk or total
+    rec = torch.full((total, 16, n), float("nan"), dtype=F64, device=batch.device) if record else None
+    core.reset(env, batch, st)
+    done = 0
+    while done < total:
+        k = min(step, total - done)
+        population.rollout(env, crit, batch, st, k, E, None if rec is None else rec[done:done + k])
+        done += k
+    met = core.episode_metrics(crit, st)
+    return PopulationResult(metrics=met, state=st, batch=batch, criteria=crit, record=rec, env=env,
+                            population=population, members=M, episodes_per_member=E)
+
+
+def evaluate_population(population: PolicyPopulation, env_config=None, num_episodes: int = 10, base_seed: int = 42,
+                        criteria: SuccessCriteria | None = None, motion=None, plant_mass=None,
+                        max_steps_per_episode: int | None = None, with_episode_metrics: bool = True) -> list:
+    """evaluate_policy's summary for every member, all members in one fused
+    launch on the same episodes (seeds base_seed + i for each member)."""
+    res = run_policy_population(population, env_config, episodes_per_member=num_episodes,
+                                seeds=base_seed + np.arange(num_episodes), motion=motion, plant_mass=plant_mass,
+                                criteria=criteria, max_steps=max_steps_per_episode)
+    out = [res.member_summary(m) for m in range(population.members)]
+    if with_episode_metrics:
+        em = res.episode_metrics()
+        for m, s in enumerate(out):
+            s.episode_metrics = em[m * num_episodes:(m + 1) * num_episodes]
+    return out

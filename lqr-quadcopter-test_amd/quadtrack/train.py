@@ -16,7 +16,10 @@ per episode) and the three means are numpy's, bit for bit, from the
 block-pairwise summary kernel (`qt_summary_numpy`).  The env is built as the
 Trainer builds it (train.py:306-312): EnvConfig defaults with the
 TrainingConfig's seed, episode length, motion type and target radius.
-Deep-policy training (the rest of train.py) is outside the hot path.
+Deep-policy training by gradient (the rest of train.py) is outside the hot
+path.  `search_policy` is a gradient-free counterpart on the population
+rollout: evolution strategies over a policy's flat weight vector, one fused
+launch of every candidate per generation.
 """
 
 from __future__ import annotations
@@ -115,3 +118,112 @@ def evaluate_epoch(config=None, epoch: int = 0, *, controller: str = "riccati_lq
     return EpochResult(mean_reward=mean_reward, mean_on_target_ratio=mean_ratio, mean_tracking_error=mean_err,
                        difficulty=1.0, episode_reward=reward[0].clone(), episode_on_target_ratio=ratio,
                        episode_tracking_error=reward[1].clone(), episode_steps=steps.to(torch.int64))
+
+
+# ------------------------------------------------------------------ policy search
+
+@dataclass
+class SearchResult:
+    """search_policy's history (host tensors, one entry per generation) and its best policy."""
+
+    centre_fitness: torch.Tensor      # [G] fitness of the unperturbed centre (member 0)
+    best_fitness: torch.Tensor        # [G] fitness of the generation's best member (the incumbent included)
+    mean_fitness: torch.Tensor        # [G] mean fitness of the perturbed members
+    incumbent_fitness: torch.Tensor   # [G] the best member so far, re-run on this generation's seeds
+    best_index: torch.Tensor          # [G] int64 member index of the generation's best
+    generation_best: torch.Tensor     # [G, P] float32 flat vector of the generation's best member
+    best_theta: torch.Tensor          # [P] float32: the last generation's best (the best so far)
+    centre: torch.Tensor              # [P] float32: the centre after the last update
+    best_policy: object               # DeepTrackingPolicy holding best_theta (save_checkpoint: reference format)
+    generations: int = 0
+    population: int = 0
+    episodes_per_member: int = 0
+
+
+def generation_seeds(env_seed: int, generation: int, episodes: int) -> np.ndarray:
+    """The reference trainer's reset seeds (train.py:662): env_seed + generation * 1000 + episode."""
+    return env_seed + generation * 1000 + np.arange(episodes)
+
+
+def centred_ranks(fitness: torch.Tensor) -> torch.Tensor:
+    """Ranks of a [K] fitness vector scaled to [-0.5, 0.5] (best: +0.5; NaN
+    ranks lowest; ties in index order: the sort is stable)."""
+    k = fitness.numel()
+    order = torch.argsort(torch.nan_to_num(fitness, nan=float("-inf")), stable=True)
+    ranks = torch.empty(k, dtype=torch.float32, device=fitness.device)
+    ranks[order] = torch.arange(k, dtype=torch.float32, device=fitness.device)
+    return ranks / max(k - 1, 1) - 0.5
+
+
+def search_policy(template=None, env_config=None, *, population: int = 16, sigma: float = 0.05,
+                  learning_rate: float = 0.05, generations: int = 10, episodes_per_member: int = 8,
+                  max_steps: int | None = None, env_seed: int = 42, seed: int = 0, fitness="tracking_error",
+                  criteria=None, motion=None, device=None) -> SearchResult:
+    """Evolution strategies over a deep policy's weights on the population rollout.
+
+    template  a DeepTrackingPolicy or its config dict: the shape, and the
+              starting centre (its weights)
+    Per generation g: `population` antithetic Gaussian perturbations (sigma;
+    noise from a torch.Generator on the device seeded with `seed`) of the
+    centre, the unperturbed centre as member 0 and the best member so far as
+    the last member: population + 2 members in one fused launch on the reset
+    seeds env_seed + g * 1000 + j, shared by all members.  The centre moves by
+    learning_rate / (population * sigma) * sum(centred rank * perturbation).
+    The best member so far is the generation's best, the re-run incumbent
+    included, so the comparison is on the same episodes.  Nothing here leaves
+    the device until the history is returned."""
+    from .controllers.deep import DeepTrackingPolicy, PolicyPopulation
+    from .policy import run_policy_population
+
+    if population < 2 or population % 2:
+        raise ValueError(f"population must be a positive even number (antithetic pairs), got {population}")
+    if not sigma > 0.0:
+        raise ValueError(f"sigma must be positive, got {sigma}")
+    if episodes_per_member < 1:
+        raise ValueError(f"episodes_per_member must be >= 1, got {episodes_per_member}")
+    if generations < 1:
+        raise ValueError(f"generations must be >= 1, got {generations}")
+    dev = _abi.require_gpu(device)
+    if not isinstance(template, DeepTrackingPolicy):
+        template = DeepTrackingPolicy(dict(template or {}), device="cpu")
+    with torch.no_grad():
+        centre = torch.nn.utils.parameters_to_vector(template.network.parameters()).detach().to(dev, torch.float32)
+    gen = torch.Generator(device=dev).manual_seed(int(seed))
+    half, E = population // 2, int(episodes_per_member)
+    best = centre.clone()
+    hist = {k: [] for k in ("centre", "best", "mean", "incumbent", "index", "theta")}
+    for g in range(generations):
+        eps = torch.randn(half, centre.numel(), generator=gen, device=dev, dtype=torch.float32)
+        eps = torch.cat([eps, -eps])
+        theta = torch.cat([centre[None], centre[None] + sigma * eps, best[None]])
+        res = run_policy_population(PolicyPopulation.from_flat(template, theta), env_config, episodes_per_member=E,
+                                    seeds=generation_seeds(env_seed, g, E), motion=motion, criteria=criteria,
+                                    max_steps=max_steps)
+        fit = res.fitness(fitness).to(torch.float64)
+        order = torch.nan_to_num(fit, nan=float("-inf"))
+        # the incumbent wins ties (it is searched first), then the lowest index
+        idx = torch.argmax(torch.cat([order[-1:], order[:-1]]))
+        idx = torch.where(idx == 0, torch.full_like(idx, theta.shape[0] - 1), idx - 1)
+        best = theta.index_select(0, idx.reshape(1))[0]
+        hist["centre"].append(fit[0])
+        hist["best"].append(fit.index_select(0, idx.reshape(1))[0])
+        hist["mean"].append(fit[1:-1].mean())
+        hist["incumbent"].append(fit[-1])
+        hist["index"].append(idx)
+        hist["theta"].append(best)
+        w = centred_ranks(fit[1:-1])
+        centre = centre + (learning_rate / (population * sigma)) * (w[:, None] * eps).sum(dim=0)
+    best_host = best.cpu()
+    cfg = dict(template.config or {})
+    cfg.pop("checkpoint_path", None)
+    net = template.network
+    cfg.update(hidden_sizes=list(net.hidden_sizes), activation=net.activation_name,
+               output_bounds=dict(net.output_bounds))
+    policy = DeepTrackingPolicy(cfg, device=str(template.device))
+    with torch.no_grad():
+        torch.nn.utils.vector_to_parameters(best_host.clone(), policy.network.parameters())
+    stack = lambda k: torch.stack(hist[k]).cpu()  # noqa: E731
+    return SearchResult(centre_fitness=stack("centre"), best_fitness=stack("best"), mean_fitness=stack("mean"),
+                        incumbent_fitness=stack("incumbent"), best_index=stack("index"),
+                        generation_best=stack("theta"), best_theta=best_host, centre=centre.cpu(),
+                        best_policy=policy, generations=generations, population=population, episodes_per_member=E)

@@ -15,6 +15,13 @@
       two synchronisations, best of --passes (default 3).  Imports nothing
       the policy feature added, so it also runs on a checkout without it.
 
+  python scripts/bench_policy.py --members 1024 [--per-member 64] [--sample 32] [--steps 300] [--passes 10]
+      Policy populations: (a) one qt_policy_population_rollout launch of
+      members x per-member episodes, (c) one qt_policy_rollout launch of as
+      many episodes with shared weights, and with --sample K
+      (b) the per-member way: K members' single-policy launches, scaled by
+      members / K.  HIP events, best of --passes.
+
 Each run prints one JSON line and appends it to --out when given.
 """
 
@@ -93,6 +100,94 @@ def fused(args):
             "timer": "HIP events around the rollout launch"}
 
 
+def _event_ms(launch, before, passes):
+    """Best of `passes` HIP-event times of launch(); before() runs outside the events; the first pass warms up."""
+    times = []
+    for _ in range(passes + 1):
+        before()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        launch()
+        e1.record()
+        e1.synchronize()
+        times.append(e0.elapsed_time(e1))
+    return min(times[1:]), [round(t, 3) for t in times[1:]]
+
+
+def population(args):
+    """(a) one population launch of --members x --per-member episodes; (c) one single-policy launch of the
+    same number of episodes (shared weights, read from global memory); with --sample K > 0 also (b) the same work as
+    per-member launches: K members' --per-member-episode single-policy launches back to back inside one
+    pair of events, scaled by members / K (stated in the line)."""
+    import quadtrack
+    from quadtrack import core
+    from quadtrack.env.config import as_env_config
+    from quadtrack.policy import policy_batch, run_policy_loop
+
+    dev = torch.device("cuda:0")
+    net = network("cpu", args.hidden)
+    template = quadtrack.DeepTrackingPolicy({"hidden_sizes": args.hidden, "activation": "relu"}, device="cpu")
+    centre = torch.nn.utils.parameters_to_vector(net.parameters()).detach()
+    M, E = args.members, args.per_member
+    g = torch.Generator().manual_seed(1)
+    theta = centre[None] + 0.05 * torch.randn(M, centre.numel(), generator=g)
+    theta[0] = centre
+    pop = quadtrack.PolicyPopulation.from_flat(template, theta, device=dev)
+    cfg = as_env_config(ENV_CFG)
+    env, crit, n = cfg.to_params(), core.criteria(), M * E
+    seeds = np.tile(np.arange(E), M)  # common random numbers
+    batch = policy_batch(cfg, n, dev, seeds=seeds)
+    st = core.RolloutState.empty(n, dev)
+    reset = lambda: core.reset(env, batch, st)  # noqa: E731
+    a_best, a_all = _event_ms(lambda: pop.rollout(env, crit, batch, st, args.steps, E), reset, args.passes)
+    a_steps = float(st.acc[quadtrack._abi.ACC_STEPS].sum())
+    shared = pop.member(0)
+    c_best, c_all = _event_ms(lambda: shared.rollout(env, crit, batch, st, args.steps), reset, args.passes)
+    c_steps = float(st.acc[quadtrack._abi.ACC_STEPS].sum())
+    waves = M * ((E + 63) // 64)
+    line = {"what": "policy_population", "network": f"{list(args.hidden)} relu", "members": M, "episodes_per_member": E,
+            "episodes": n, "steps": args.steps, "passes": args.passes, "waves": waves,
+            "lane_utilisation": n / (64.0 * waves), "block_bytes_per_member": 4 * pop.block_floats,
+            # weights run from LDS when four waves' blocks fit 160 KiB, unless QT_POPULATION_STAGE=0
+            "staged_in_lds": 4 * 4 * ((pop.block_floats + 63) // 64 * 64) <= 160 * 1024
+            and not os.environ.get("QT_POPULATION_STAGE", "1").startswith("0"),
+            "a_population_ms_best": a_best, "a_population_ms_all": a_all, "a_env_steps": a_steps,
+            "a_ns_per_env_step": a_best * 1e6 / a_steps,
+            "c_shared_weights_ms_best": c_best, "c_shared_weights_ms_all": c_all, "c_env_steps": c_steps,
+            "a_over_c": a_best / c_best, "timer": "HIP events around the rollout launch (the reset is outside)"}
+    K = min(args.sample, M)
+    if K > 0:
+        members = [pop.member(m) for m in range(K)]
+        sub = policy_batch(cfg, E, dev, seeds=np.arange(E))
+        states = [core.RolloutState.empty(E, dev) for _ in range(K)]
+
+        def reset_all():
+            for s in states:
+                core.reset(env, sub, s)
+
+        def launch_all():
+            for p, s in zip(members, states):
+                p.rollout(env, crit, sub, s, args.steps)
+
+        b_best, b_all = _event_ms(launch_all, reset_all, args.passes)
+        # the whole of run_policy_loop per member (batch, reset, launch, metrics), wall clock: what a caller pays
+        walls = []
+        for _ in range(3):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for p in members:
+                run_policy_loop(p, cfg, n=E, seeds=np.arange(E), max_steps=args.steps)
+            torch.cuda.synchronize()
+            walls.append((time.perf_counter() - t0) * 1e3)
+        line.update({"b_sample_members": K, "b_sample_launches_ms_best": b_best, "b_sample_launches_ms_all": b_all,
+                     "b_per_member_launches_ms_scaled": b_best * M / K, "a_over_b": a_best / (b_best * M / K),
+                     "b_run_policy_loop_wall_ms_scaled": min(walls) * M / K,
+                     "a_over_b_run_policy_loop_wall": a_best / (min(walls) * M / K),
+                     "b_note": f"{K} of {M} members timed ({E}-episode qt_policy_rollout launches back to back in one "
+                               f"event pair; run_policy_loop calls by wall clock, best of 3), scaled by {M}/{K}"})
+    return line
+
+
 def baseline(args):
     import quadtrack
 
@@ -134,13 +229,17 @@ def main():
     ap.add_argument("--passes", type=int, default=None)
     ap.add_argument("--hidden", default="64,64", help="hidden layer sizes, comma-separated")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--members", type=int, default=0, help="population mode: members of one fused launch")
+    ap.add_argument("--per-member", type=int, default=64, help="population mode: episodes per member")
+    ap.add_argument("--sample", type=int, default=0,
+                    help="population mode: members whose single-policy launches are timed and scaled (0: skip)")
     args = ap.parse_args()
     args.hidden = [int(v) for v in args.hidden.split(",")]
     if args.steps is None:
-        args.steps = 300 if args.baseline else 3000
+        args.steps = 300 if args.baseline or args.members else 3000
     if args.passes is None:
         args.passes = 3 if args.baseline else 10
-    line = baseline(args) if args.baseline else fused(args)
+    line = population(args) if args.members else baseline(args) if args.baseline else fused(args)
     line["device"] = torch.cuda.get_device_name(0)
     text = json.dumps(line)
     print(text)
