@@ -554,6 +554,15 @@ struct Horizon {
   // run_yaw0's DUAL: a tilt-bounded horizon shorter than this tries the
   // clamping no-vote body (kDualBelow; 0 never does, for the bitwise test)
   int dual_below;
+  // The rate-command clips (rate_distance, qt_kernels.hpp): the level the raw
+  // roll / pitch rate commands must stay under, max_rate less a relative
+  // margin for the rounding of the command's few operations, and the per-step
+  // time bound 1 / inv_tstep (a linear target's reach per step is |v| tstep).
+  // rate_on == 0 (QT_RATE_HORIZON=0, a test knob): the rate term reports no
+  // distance, so every step is voted and clipped.
+  int rate_on;
+  double rate_lim;
+  double tstep;
 };
 
 QT_HD Horizon make_horizon(const qt_env_params& e, const qt_ctrl_params& c, const RateLin& rl) {
@@ -576,6 +585,9 @@ QT_HD Horizon make_horizon(const qt_env_params& e, const qt_ctrl_params& c, cons
   h.inv_dang = 1.0 / ((fabs(rl.ay) + fabs(rl.au)) * c.max_rate * (1.0 + 1e-9) + 2e-15);
   h.inv_tstep = 1.0 / ((e.dt + (fabs(e.max_episode_time) + e.dt) * 4.5e-16) * (1.0 + 1e-9));
   h.slack = 1.0 + 1e-9;
+  h.rate_on = 1;
+  h.rate_lim = c.max_rate * (1.0 - 1e-9);
+  h.tstep = (e.dt + (fabs(e.max_episode_time) + e.dt) * 4.5e-16) * (1.0 + 1e-9);
   {
     // dt = m 2^q with m odd: the lowest set bit 2^q is half an ulp of t
     // for t in [2^(q + 53), 2^(q + 54))
@@ -1255,7 +1267,11 @@ __device__ __forceinline__ double add_product_rn(double a, double b, double c) {
 // command is finite and np.clip's NaN pass-through cannot arise.
 // FF: the feed-forward arithmetic is compiled in (some lane may have it on);
 // its parameters are the lane's, `f` (ff_uniform / qt_batch.ff).
-template <int KC, bool FF, bool KS, bool FAST = false>
+// NORATE (a no-vote step of the yaw-at-rest loop whose horizon bounds the rate
+// commands, rate_distance): the raw roll / pitch rate commands are known to
+// lie inside +-max_rate, where the clip returns its operand's bits, so it is
+// left out.
+template <int KC, bool FF, bool KS, bool FAST = false, bool NORATE = false>
 __device__ __forceinline__ bool compute_action(const qt_ctrl_params& c, const Gains<KC, KS>& G, double hover,
                                                const double* qp, const double* qv, const Target& tg,
                                                const FFLane& f, double* integ, double* u, double* diag = nullptr,
@@ -1363,8 +1379,8 @@ __device__ __forceinline__ bool compute_action(const qt_ctrl_params& c, const Ga
   const double raw2 = FF ? uf[2] + ffa[0] : uf[2];
   const double raw3 = uf[3];
   u[0] = clip_num(raw0, c.min_thrust, c.max_thrust);
-  u[1] = clip_num(raw1, -c.max_rate, c.max_rate);
-  u[2] = clip_num(raw2, -c.max_rate, c.max_rate);
+  u[1] = NORATE ? raw1 : clip_num(raw1, -c.max_rate, c.max_rate);
+  u[2] = NORATE ? raw2 : clip_num(raw2, -c.max_rate, c.max_rate);
   // structured gains have no yaw row: clip(0, -max_rate, max_rate) = 0 for
   // the max_rate >= 0 that fast_path_ok requires
   u[3] = (KS && FAST) ? 0.0 : clip_num(raw3, -c.max_rate, c.max_rate);

@@ -648,7 +648,9 @@ __device__ __forceinline__ void tilt_clamp(double* x, Trig& ta) {
 // wave can stop at, so the wave runs them without the stop vote.  Each lane
 // bounds its distance to every stop condition the vote tests by the per-step
 // bounds of Horizon (LaunchConst::hz): speed from the velocity clamp's guard,
-// the position bound, (TILT) roll / pitch from the tilt clamp, the time limit;
+// the position bound, (TILT) roll / pitch from the tilt clamp, the time limit,
+// and (RATE) the raw rate commands' distance to their clip, which the
+// horizon's steps then leave out (rate_distance, above);
 // the wave takes the minimum over its active lanes by ballots (inactive lanes
 // cast no vote).  The bounds hold for the state the loop is in at every
 // step start (finite, |v| below the clamp, |w| and |u| within max_rate:
@@ -657,9 +659,79 @@ __device__ __forceinline__ void tilt_clamp(double* x, Trig& ta) {
 constexpr int kMaxHorizon = 62;
 constexpr int kVotedBurst = 4;
 
-template <bool TILT, bool BINADE>
+// Distance of the raw roll / pitch rate commands to their clip, in steps
+// (run_yaw0's kRate loops: 6-column gains, no feed-forward, a stationary or
+// linear target).  Row r = 1, 2 of the gains gives raw_r = sum_j K_rj s_j with
+// the six controller errors s = (p_T - p, v_T - v) of the observation, and
+// per step and component
+//   a position error moves by <= dp + |v_T,j| tstep   (dp: yaw0_horizon's
+//     position bound; the target p_T = center + v_T t is evaluated from t,
+//     tstep bounds t' - t and pabs the rounding of p_T),
+//   a velocity error moves by <= (1 - cv) vmax + |T| / m sum_i |wv_i| + |gv|
+//     (v'_j = cv v_j + sum_i wv_i acc_ij + gv_j with |v_j| <= vmax at every
+//     step start and |acc_ij| <= |T| / m; v_T is constant),
+// the latter widened by slack and vabs like its neighbours.  So j steps on
+//   |raw_r| <= sum_j |K_rj| |s_j| + j sum_j |K_rj| delta_j,
+// which stays under rate_lim = max_rate (1 - 1e-9) for every
+//   j < h_r = (rate_lim - sum_j |K_rj| |s_j|) / sum_j |K_rj| delta_j;
+// the margin covers the rounding of raw_r's sum.  A clip of a finite value
+// inside its range returns that value's bits (fmin(fmax(v, lo), hi) = v for
+// lo <= v <= hi, -0.0 included, also in this unit's non-IEEE min / max: no
+// operand is a NaN), so a no-vote step without the two rate clips is still
+// exactly a voted step that did not stop.  The thrust clip stays: the same
+// reasoning bounds it for ~25 steps only (k_vz times the speed bound).
+// rate_on == 0: no distance, every step is voted (and clipped).
+template <int KC, bool KS>
+__device__ __forceinline__ double rate_distance(const Horizon& hz, const VelLin& lin, const Plant& pl,
+                                                const Gains<KC, KS>& G, const Target& tg, const double* x) {
+  static_assert(KC == 6, "6-column gains");
+  const double tmi = hz.tmax * pl.inv_mass;
+  const double sw = (fabs(lin.wv[0]) + fabs(lin.wv[1])) + (fabs(lin.wv[2]) + fabs(lin.wv[3]));
+  const double spa = (fabs(lin.pa[0]) + fabs(lin.pa[1])) + fabs(lin.pa[2]);
+  const double dp = fma(fma(fabs(lin.pv), hz.vmax, fma(tmi, spa, fabs(lin.gp))), hz.slack, hz.pabs);  // yaw0_horizon's
+  const double dvc = fma(fma(1.0 - lin.cv, hz.vmax, fma(tmi, sw, fabs(lin.gv))), hz.slack, hz.vabs);
+  // (a factor 1 the optimiser cannot see through, re-made at every call: the
+  // per-lane constants below would otherwise be hoisted out of run_yaw0's
+  // loops and stay live across the step loop — dense gains, linear target:
+  // 258 registers and one wave per SIMD where 232 left room for two)
+  double one = 1.0;
+  asm volatile("" : "+v"(one));
+  double s[6], d[6];
+#pragma unroll
+  for (int j = 0; j < 3; ++j) {
+    s[j] = fabs(tg.p[j] - x[j]);
+    s[3 + j] = fabs(tg.v[j] - x[3 + j]);
+    d[j] = fma(fabs(tg.v[j]), hz.tstep, dp + hz.pabs) * one;
+    d[3 + j] = dvc * one;
+  }
+  double h = INFINITY;
+#pragma unroll
+  for (int r = 1; r <= 2; ++r) {
+    double num = hz.rate_lim, den = 1e-300;  // (den > 0: the reciprocal is finite)
+    if constexpr (KS) {
+      // row 1: K[1][1], K[1][4] (slots 2, 3); row 2: K[2][0], K[2][3] (slots 4, 5)
+      const int j = r == 1 ? 1 : 0;
+      const double kp = fabs(G.k[2 * r]), kv = fabs(G.k[2 * r + 1]);
+      num = fma(-kv, s[3 + j], fma(-kp, s[j], num));
+      den = fma(kv, d[3 + j], fma(kp, d[j], den));
+    } else {
+#pragma unroll
+      for (int j = 0; j < 6; ++j) {
+        const double ka = fabs(G.k[r * KC + j]);
+        num = fma(-ka, s[j], num);
+        den = fma(ka, d[j], den);
+      }
+    }
+    h = fmin(h, num * __builtin_amdgcn_rcp(den));
+  }
+  return hz.rate_on ? h : 0.0;
+}
+
+// h_more: a further per-lane distance in steps (rate_distance; RATE)
+template <bool TILT, bool BINADE, bool RATE = false>
 __device__ __forceinline__ int yaw0_horizon(const qt_env_params& e, const Horizon& hz, const VelLin& lin,
-                                            const Plant& pl, const double* x, double t, int rem) {
+                                            const Plant& pl, const double* x, double t, int rem,
+                                            double h_more = 0.0) {
   const double tmi = hz.tmax * pl.inv_mass;
   const double sw = (fabs(lin.wv[0]) + fabs(lin.wv[1])) + (fabs(lin.wv[2]) + fabs(lin.wv[3]));
   const double spa = (fabs(lin.pa[0]) + fabs(lin.pa[1])) + fabs(lin.pa[2]);
@@ -671,6 +743,7 @@ __device__ __forceinline__ int yaw0_horizon(const qt_env_params& e, const Horizo
   h = fmin(h, (hz.pmax - fmax(fabs(x[0]), fmax(fabs(x[1]), fabs(x[2])))) * __builtin_amdgcn_rcp(dp));
   if (TILT) h = fmin(h, (kMaxTilt - fmax(fabs(x[6]), fabs(x[7]))) * hz.inv_dang);
   h = fmin(h, (e.max_episode_time - t) * hz.inv_tstep);
+  if constexpr (RATE) h = fmin(h, h_more);
   bool bin_ok = true;
   if (BINADE) {
     // t stays inside its binade [2^E, 2^(E+1)) and the binade has no tie, so
@@ -733,7 +806,13 @@ __device__ __forceinline__ void ride_target(const qt_env_params& e, bool still, 
   }
 }
 
-template <int MOTION, int KC, bool FF, bool KS, bool UNI, bool DUAL = false, bool RIDE = false>
+// EQR (the host takes it when cr.target_radius and e.target_radius have equal
+// bits): the env's post-step on-target test of step k reads the error and
+// the radius of the metrics' pre-step test of step k + 1, so over a run of
+// steps sum(post flags) = sum(pre flags) - first pre flag + the flag of the
+// run's final error: on_post takes no per-step work and is rebuilt from
+// on_pre after each run.
+template <int MOTION, int KC, bool FF, bool KS, bool UNI, bool DUAL = false, bool RIDE = false, bool EQR = false>
 __device__ __forceinline__ void run_yaw0(const qt_env_params& e, const qt_ctrl_params& c, const qt_criteria& cr,
                                          int motion, const Pattern& pt, const Plant& pl_lane, double hover,
                                          const Gains<KC, KS>& G, const FFLane& fl, double* x, double* integ,
@@ -788,10 +867,19 @@ __device__ __forceinline__ void run_yaw0(const qt_env_params& e, const qt_ctrl_p
   // loops sit at 256 architectural VGPRs and answer it with ~17 register
   // copies per step (circular 237 -> 243), so they keep the per-step rotor.
   constexpr bool kFold = kRotor && KC == 9;
+  // The horizon also bounds the raw roll / pitch rate commands (rate_distance)
+  // and its steps run without their clips: 6-column gains without
+  // feed-forward on a stationary or linear target (a rider's is stationary).
+  // The periodic targets, LQI, PID and feed-forward keep the clips.
+  constexpr bool kRate = KC == 6 && !FF && (MOTION == QT_MOTION_STATIONARY || MOTION == QT_MOTION_LINEAR);
+  constexpr bool kEqr = EQR && !(QT_ABLATE & QT_ABL_METRICS);
   int s = 0;
   while (a.term == QT_TERM_RUNNING && s < nsteps) {
     const int s0 = s;
     int rem = nsteps - s0 > (1 << 29) ? (1 << 29) : nsteps - s0;  // steps left in this run (z stays < 1 off phase)
+    // kEqr: on_post less the pre flags before this run and the run's first
+    // (one live count across the loop instead of two)
+    if constexpr (kEqr) on_post -= on_pre + (int)(err <= R);
     RateCoef rk;
     // one closed-loop step; VOTE: end it with the stop vote (true: stop here)
     auto step = [&](auto vote, auto clamp, const double* fc, const double* fs) -> bool {
@@ -806,7 +894,7 @@ __device__ __forceinline__ void run_yaw0(const qt_env_params& e, const qt_ctrl_p
         if constexpr (KC == 3)
           compute_action_pid<FF, true>(c, G.k, hover, x, x + 3, tg, t, fl, integ, u);  // observation time = t
         else
-          compute_action<KC, FF, KS, true>(c, G, hover, x, x + 3, tg, fl, integ, u, nullptr, err);
+          compute_action<KC, FF, KS, true, kRate && !VOTE>(c, G, hover, x, x + 3, tg, fl, integ, u, nullptr, err);
       }
       // ---- the Evaluator's pre-step record (eval.py:142-159) -> metrics
       if (!(QT_ABLATE & QT_ABL_METRICS)) {
@@ -819,7 +907,11 @@ __device__ __forceinline__ void run_yaw0(const qt_env_params& e, const qt_ctrl_p
         const bool counted = on & (z > W);
         os_count += counted;
         a.os_max = counted ? fmax(a.os_max, cur) : a.os_max;
-        cur = on ? err - R : fmax(cur, err - R);
+        // cur = on ? err - R : fmax(cur, err - R) as one maximum: on target
+        // err - R <= 0, so any finite number below -R in cur's place gives
+        // the same bits, and replacing cur's high word makes one (0xffefffff:
+        // <= -1.797e308 with every low word, never a NaN as -inf's would be)
+        cur = fmax(__hiloint2double(on ? (int)0xffefffff : __double2hiint(cur), __double2loint(cur)), err - R);
         z = on ? 1 : z + 1;
       }
       // ---- env.step (quadcopter_env.py:152-232): the command is finite and
@@ -846,7 +938,7 @@ __device__ __forceinline__ void run_yaw0(const qt_env_params& e, const qt_ctrl_p
       // post-step tracking error: the env's on-target count now, the next
       // step's pre-step error (positions are not constrained)
       err = sqrt_pos(sq3_ref(x[0] - tg.p[0], x[1] - tg.p[1], x[2] - tg.p[2]));
-      on_post += err <= eR;
+      if constexpr (!kEqr) on_post += err <= eR;
       // angle wrap (no correction: tilt-bounded), carried roll / pitch trig of
       // the wrapped angles (attitude_trig_resid's bound holds for them), then
       // the tilt clamp on both the angles and their trig (tilt_clamp): here,
@@ -869,11 +961,13 @@ __device__ __forceinline__ void run_yaw0(const qt_env_params& e, const qt_ctrl_p
     // The safe horizon's steps without the vote (four per back edge, then
     // the horizon's last two); voted steps only where no horizon is left.
     do {
-      int H = yaw0_horizon<kTiltHorizon, kFold>(e, k.hz, lin, pl, x, t, rem);
+      double hr = 0.0;
+      if constexpr (kRate) hr = rate_distance<KC, KS>(k.hz, lin, pl, G, tg, x);
+      int H = yaw0_horizon<kTiltHorizon, kFold, kRate>(e, k.hz, lin, pl, x, t, rem, hr);
       bool clamp_body = false;  // wave-uniform (H comes from ballots)
       if constexpr (DUAL) {
         if (H < k.hz.dual_below) {
-          const int H2 = yaw0_horizon<false, kFold>(e, k.hz, lin, pl, x, t, rem);
+          const int H2 = yaw0_horizon<false, kFold, kRate>(e, k.hz, lin, pl, x, t, rem, hr);
           if (H2 > H) H = H2, clamp_body = true;
         }
       }
@@ -930,6 +1024,9 @@ __device__ __forceinline__ void run_yaw0(const qt_env_params& e, const qt_ctrl_p
     const int ran = (nsteps - s0 > (1 << 29) ? (1 << 29) : nsteps - s0) - rem;
     s += ran;
     a.steps += ran;
+    // kEqr: the run's post-step flags from its pre-step ones (before the exact
+    // finish below; it changes neither err nor the counts)
+    if constexpr (kEqr) on_post += on_pre + (int)(err <= R);
     stepped = true;
     z = z <= 0 ? kNeg : z;  // off phase: keep z far below 1 for the next run
     // finish the last step exactly: the velocity clamp where it acts and
@@ -958,7 +1055,7 @@ __device__ __forceinline__ void run_yaw0(const qt_env_params& e, const qt_ctrl_p
 // (lc.reward); without them the exact loop carries neither pointer.  INTEG
 // (the exact flavour): the integrator, known at launch (integrate_closed).
 template <int FLAVOR, int MOTION, int KC, bool FF, bool KS, bool UNI = false, bool FRESH = true, bool REC = true,
-          int INTEG = -1, bool RIDE = false, bool PIN = true>
+          int INTEG = -1, bool RIDE = false, bool PIN = true, bool EQR = false>
 __device__ __forceinline__ void rollout_lane(const qt_env_params& e, const qt_ctrl_params& c, const qt_criteria& cr,
                                              const BatchDev& b, const qt_state& st, int nsteps,
                                              double* __restrict__ rec, int deferred, const LaunchConst& lc,
@@ -1079,7 +1176,7 @@ __device__ __forceinline__ void rollout_lane(const qt_env_params& e, const qt_ct
       run_yaw0<MOTION, KC, FF, KS, UNI,
                (FRESH || QT_GROUPED_DUAL) && KC != 9 &&
                    (MOTION == QT_MOTION_CIRCULAR || MOTION == QT_MOTION_SINUSOIDAL || MOTION == QT_MOTION_FIGURE8),
-               RIDE>(e, c, cr, motion, pt, pl, hover, G, fl, x, integ, tg, t, a, nsteps, lc, still);
+               RIDE, EQR>(e, c, cr, motion, pt, pl, hover, G, fl, x, integ, tg, t, a, nsteps, lc, still);
     else
       run_steps<true, MOTION, KC, FF, KS>(e, c, cr, motion, pt, pl, hover, G, fl, x, integ, tg, t, a, nsteps, rec,
                                           n, ep);
@@ -1118,8 +1215,10 @@ __device__ __forceinline__ void rollout_lane(const qt_env_params& e, const qt_ct
   if (FRESH && lc.met) store_metrics(cr, a, t, lc.met, n, ep);  // a fresh pass: the metrics rows (metrics_kernel)
 }
 
+// EQR (yaw-at-rest, 6-column gains, no feed-forward): run_yaw0's variant for
+// equal on-target radii, chosen by the host (launch_fast's eqr).
 template <int FLAVOR, int MOTION, int KC, bool FF, bool KS, bool UNI = false, bool REC = true, int INTEG = -1,
-          bool PIN = true>
+          bool PIN = true, bool EQR = false>
 __global__ __launch_bounds__(kBlock) void rollout_kernel(qt_env_params e, qt_ctrl_params c, qt_criteria cr,
                                                          BatchDev b, qt_state st, int nsteps,
                                                          double* __restrict__ rec, int deferred, LaunchConst lc) {
@@ -1128,8 +1227,8 @@ __global__ __launch_bounds__(kBlock) void rollout_kernel(qt_env_params e, qt_ctr
   if (FLAVOR == kExact && deferred != kExact && lc.defer_flag && *lc.defer_flag != lc.epoch) return;
   const int64_t slot = slot_at(b, (int64_t)blockIdx.x * kBlock + threadIdx.x);
   if (slot < 0) return;
-  rollout_lane<FLAVOR, MOTION, KC, FF, KS, UNI, true, REC, INTEG, false, PIN>(e, c, cr, b, st, nsteps, rec, deferred, lc,
-                                                                             slot);
+  rollout_lane<FLAVOR, MOTION, KC, FF, KS, UNI, true, REC, INTEG, false, PIN, EQR>(e, c, cr, b, st, nsteps, rec,
+                                                                                  deferred, lc, slot);
 }
 
 // The yaw-at-rest fast flavour over a batch grouped by motion type
@@ -1229,9 +1328,14 @@ inline bool valid_state(const qt_state& st, bool need_integ) {
 // uni: no per-episode mass, hover thrust or gains (rollout_kernel's UNI).
 // grouped: the yaw-at-rest flavour of a motion-grouped batch in one launch
 // (rollout_grouped_kernel; `motion` is ignored).
+// eqr: the criteria's and the env's on-target radii have equal bits; the
+// yaw-at-rest kernels with 6-column gains, no feed-forward and a stationary
+// or linear target then take run_yaw0's EQR variant (the periodic targets'
+// kernels sit at the 256-register edge, where the variant costs the figure-8
+// loop its second wave per SIMD; the grouped kernel has none either).
 void launch_fast(int flavor, bool uni, bool grouped, int kc, bool ff, bool ks, int motion, int grid, hipStream_t s,
                  const qt_env_params& e, const qt_ctrl_params& c, const qt_criteria& cr, const BatchDev& b,
-                 const qt_state& st, int nsteps, const LaunchConst& lc);
+                 const qt_state& st, int nsteps, const LaunchConst& lc, bool eqr);
 
 // The pair-lane yaw-at-rest flavour (qt_pair.hpp; qt_rollout_fast.hip): one
 // episode on two lanes, for a batch of at most one wave per SIMD in pairs;

@@ -644,6 +644,21 @@ int dual_below() {
   return (int)x;
 }
 
+// The rate-command term of the yaw-at-rest loop's safe horizon (rate_distance,
+// qt_kernels.hpp): on unless QT_RATE_HORIZON=0 (a test knob, read at each
+// launch: the term then reports no distance, so every step of the loops that
+// have it is voted and clipped — the arithmetic without the term, step for
+// step — and a test can compare the two bit for bit).  Any other value than 0
+// or 1 is ignored (the term stays on) and reported once on stderr.
+int rate_horizon_on() {
+  const char* s = getenv("QT_RATE_HORIZON");
+  if (!s || !*s) return 1;
+  if ((s[0] == '0' || s[0] == '1') && s[1] == '\0') return s[0] == '1';
+  static std::atomic<bool> warned{false};
+  if (!warned.exchange(true)) fprintf(stderr, "quadtrack: ignoring QT_RATE_HORIZON=%s (not 0 or 1)\n", s);
+  return 1;
+}
+
 // The pair-lane yaw-at-rest flavour (qt_pair.hpp): on unless QT_PAIR=0 (an
 // A/B and test knob, read at each launch).
 bool pair_on() {
@@ -726,6 +741,9 @@ int launch_rollout(int kc, bool ff, bool ks, bool no_yaw, int motion, int grid, 
   LaunchConst lc = make_launch_const(e);  // yaw-at-rest closed forms, target rotors
   lc.hz = make_horizon(e, c, lc.rl);       // the yaw-at-rest loop's safe horizon
   lc.hz.dual_below = dual_below();
+  lc.hz.rate_on = lc.hz.on ? rate_horizon_on() : 0;
+  // equal on-target radii (bit for bit): run_yaw0's EQR variant
+  const bool eqr = memcmp(&cr.target_radius, &e.target_radius, sizeof(double)) == 0;
   lc.reward = reward;
   lc.fresh_off = fresh_off, lc.met = met;  // qt_rollout_fresh: reset in the prologue, metrics in the epilogue
   const bool ks_eff = ks || kc == 3;
@@ -739,7 +757,7 @@ int launch_rollout(int kc, bool ff, bool ks, bool no_yaw, int motion, int grid, 
     if (flavor == kYaw0 && pair_fits(kc, ff, ks, grouped, motion, b, lc))
       launch_pair(motion, (int)((2 * b.n + kBlock - 1) / kBlock), s, e, c, cr, b, st, nsteps, lc);
     else
-      launch_fast(flavor, uni, grouped, kc, ff, ks_eff, motion, grid, s, e, c, cr, b, st, nsteps, lc);
+      launch_fast(flavor, uni, grouped, kc, ff, ks_eff, motion, grid, s, e, c, cr, b, st, nsteps, lc, eqr);
     if (hipGetLastError() != hipSuccess) return QT_ELAUNCH;
     lc.fresh_off = nullptr;  // the fast kernel stored the reset state of the waves it left
   }

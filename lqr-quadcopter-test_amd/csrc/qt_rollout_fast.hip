@@ -30,12 +30,21 @@ namespace qtk {
 namespace {
 struct FastLaunch {
   template <int MOTION, int KC, bool FF, bool KS>
-  static void run(int flavor, bool uni, int grid, hipStream_t s, const qt_env_params& e, const qt_ctrl_params& c,
-                  const qt_criteria& cr, const BatchDev& b, const qt_state& st, int nsteps, const LaunchConst& lc) {
+  static void run(int flavor, bool uni, bool eqr, int grid, hipStream_t s, const qt_env_params& e,
+                  const qt_ctrl_params& c, const qt_criteria& cr, const BatchDev& b, const qt_state& st, int nsteps,
+                  const LaunchConst& lc) {
     // (uni, the SGPR-resident plant / gain variant, is not instantiated: with
     // the closed-form and launch constants it overflows the 102 SGPRs and
     // spills through v_writelane / v_readlane in the step loop)
     (void)uni;
+    // equal on-target radii: run_yaw0's EQR variant, where it is instantiated
+    if constexpr (KC == 6 && !FF && (MOTION == QT_MOTION_STATIONARY || MOTION == QT_MOTION_LINEAR)) {
+      if (flavor == kYaw0 && eqr) {
+        rollout_kernel<kYaw0, MOTION, KC, FF, KS, false, true, -1, true, true><<<grid, kBlock, 0, s>>>(
+            e, c, cr, b, st, nsteps, nullptr, kExact, lc);
+        return;
+      }
+    }
     if (flavor == kYaw0)
       rollout_kernel<kYaw0, MOTION, KC, FF, KS><<<grid, kBlock, 0, s>>>(e, c, cr, b, st, nsteps, nullptr, kExact, lc);
     else
@@ -55,11 +64,11 @@ struct GroupedLaunch {
 
 void launch_fast(int flavor, bool uni, bool grouped, int kc, bool ff, bool ks, int motion, int grid, hipStream_t s,
                  const qt_env_params& e, const qt_ctrl_params& c, const qt_criteria& cr, const BatchDev& b,
-                 const qt_state& st, int nsteps, const LaunchConst& lc) {
+                 const qt_state& st, int nsteps, const LaunchConst& lc, bool eqr) {
   if (grouped && flavor == kYaw0)
     dispatch_rollout<GroupedLaunch>(kc, ff, ks, -1, grid, s, e, c, cr, b, st, nsteps, lc);
   else
-    dispatch_rollout<FastLaunch>(kc, ff, ks, motion, flavor, uni, grid, s, e, c, cr, b, st, nsteps, lc);
+    dispatch_rollout<FastLaunch>(kc, ff, ks, motion, flavor, uni, eqr, grid, s, e, c, cr, b, st, nsteps, lc);
 }
 
 namespace {
