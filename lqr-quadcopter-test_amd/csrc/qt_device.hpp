@@ -153,8 +153,14 @@ __device__ __forceinline__ int periodic_angles(int motion, const Pattern& pt, do
 
 // Figure-8 position / velocity (target_motion.py:173-204) from sin / cos of
 // theta = omega t, without the acceleration: the four divisions by den and
-// den^2 as one reciprocal (within an ulp) and products (<= 3 ulp per
-// component; without feed-forward no forward difference reads them).
+// den^2 as one reciprocal (within an ulp of 1 / den; correctly rounded on
+// every argument measured) and products.  Against the exact quotients at the
+// same st, ct the device is within 2.3 / 3.0 ulp (p[0], p[1]), 4.8 ulp (v[0])
+// and 4.0 ulp of amplitude * omega (v[1], whose numerator cancels); the
+// separately rounded float64 form of these expressions allows 4.4 / 4.5 /
+// 8.0 / 5.2 with the reciprocal an ulp off (tests/test_gpu_device_math.py,
+// profiles/r12/device_math_probe.txt).  Without feed-forward no forward
+// difference reads them.
 __device__ __forceinline__ void figure8_recip(const qt_env_params& e, double om, double st, double ct, Target& o) {
   const double sc = e.amplitude;
   const double den = 1.0 + st * st;
@@ -180,8 +186,8 @@ __device__ __forceinline__ void figure8_recip(const qt_env_params& e, double om,
 // which only the feed-forward path reads (riccati_lqr.py:853-861).
 // RECIP (fast step, no acceleration wanted): the figure-8's four divisions
 // by den and den^2 become one reciprocal (within an ulp) and products
-// (<= 3 ulp per component; without feed-forward no forward difference reads
-// them).
+// (measured <= 3 ulp for the position, <= 5 ulp for the velocity components,
+// see figure8_recip; without feed-forward no forward difference reads them).
 template <bool WANT_ACC, bool RECIP = false>
 __device__ __forceinline__ void target_state(const qt_env_params& e, int motion, const Pattern& pt, double t,
                                              Target& o) {

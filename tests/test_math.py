@@ -22,6 +22,16 @@ int main(int argc, char** argv) {
   while (fread(&v, 8, 1, f) == 1) x.push_back(v);
   fclose(f);
   FILE* o = fopen(argv[2], "wb");
+  if (argc > 3) {  // rotate_cm on (s0, c0, sd, cm) quadruples
+    for (size_t i = 0; i + 3 < x.size(); i += 4) {
+      double s, c;
+      qt::rotate_cm(x[i], x[i + 1], x[i + 2], x[i + 3], &s, &c);
+      fwrite(&s, 8, 1, o);
+      fwrite(&c, 8, 1, o);
+    }
+    fclose(o);
+    return 0;
+  }
   for (double a : x) {
     double s, c;
     qt::fast_sincos(a, &s, &c);
@@ -32,6 +42,8 @@ int main(int argc, char** argv) {
     qt::rate_sincos(a, &sr, &cr);
     double sq, cq;
     qt::resid_sincos(a, &sq, &cq);
+    double sy, cy;
+    qt::tiny_sincos(a, &sy, &cy);
     fwrite(&s, 8, 1, o);
     fwrite(&c, 8, 1, o);
     fwrite(&m, 8, 1, o);
@@ -43,6 +55,8 @@ int main(int argc, char** argv) {
     fwrite(&cr, 8, 1, o);
     fwrite(&sq, 8, 1, o);
     fwrite(&cq, 8, 1, o);
+    fwrite(&sy, 8, 1, o);
+    fwrite(&cy, 8, 1, o);
   }
   fclose(o);
   return 0;
@@ -50,21 +64,64 @@ int main(int argc, char** argv) {
 """
 
 
-@pytest.fixture(scope="module")
-def probe(tmp_path_factory):
-    d = tmp_path_factory.mktemp("math")
-    (d / "p.cpp").write_text(SRC)
-    exe = d / "p"
-    subprocess.run(["g++", "-O2", "-std=c++17", "-ffp-contract=off", "-I", os.path.join(PKG, "csrc"),
-                    str(d / "p.cpp"), "-o", str(exe)], check=True)
+def _host_has_fma():
+    try:
+        return " fma " in open("/proc/cpuinfo").read().replace("\n", " ")
+    except OSError:
+        return False
 
-    def run(x):
+
+def _rocm_clang():
+    for root in (os.environ.get("ROCM_PATH"), "/opt/rocm"):
+        for sub in ("llvm/bin/clang++", "lib/llvm/bin/clang++"):
+            if root and os.path.exists(os.path.join(root, sub)):
+                return os.path.join(root, sub)
+    return None
+
+
+# The host builds of the probe.  "separate": every operation rounded on its own
+# (the sequence numpy-style references assume).  "contract": ROCm's clang with
+# the library's own rule, -ffp-contract=on (Makefile HIPFLAGS) and FMA
+# instructions: a * b + c inside one expression becomes an fma, as in the
+# gfx950 code (tests/test_gpu_device_math.py holds the device to this build bit
+# for bit).
+HOST_BUILDS = ("separate", "contract")
+PROBE_COLS = 13
+
+
+def build_host_probe(d, build):
+    """Compile SRC in directory d; returns run(x) -> [len(x), PROBE_COLS] and
+    run(quads, rotate=True) -> [len(quads), 2] (rotate_cm)."""
+    if build == "separate":
+        cmd = ["g++", "-O2", "-std=c++17", "-ffp-contract=off"]
+    else:
+        clang = _rocm_clang()
+        if clang is None:
+            pytest.skip("ROCm's clang is not installed")
+        if not _host_has_fma():
+            pytest.skip("the host has no FMA instructions")
+        cmd = [clang, "-O2", "-std=c++17", "-mfma", "-ffp-contract=on"]
+    (d / "p.cpp").write_text(SRC)
+    exe = d / f"p_{build}"
+    subprocess.run(cmd + ["-I", os.path.join(PKG, "csrc"), str(d / "p.cpp"), "-o", str(exe)], check=True)
+
+    def run(x, rotate=False):
         x = np.ascontiguousarray(x, dtype=np.float64)
         (d / "in.bin").write_bytes(x.tobytes())
-        subprocess.run([str(exe), str(d / "in.bin"), str(d / "out.bin")], check=True)
-        return np.frombuffer((d / "out.bin").read_bytes(), dtype=np.float64).reshape(-1, 11)
+        subprocess.run([str(exe), str(d / "in.bin"), str(d / "out.bin")] + (["rotate"] if rotate else []), check=True)
+        return np.frombuffer((d / "out.bin").read_bytes(), dtype=np.float64).reshape(-1, 2 if rotate else PROBE_COLS)
 
     return run
+
+
+@pytest.fixture(scope="module")
+def probe(tmp_path_factory):
+    return build_host_probe(tmp_path_factory.mktemp("math"), "separate")
+
+
+@pytest.fixture(scope="module")
+def probe_contract(tmp_path_factory):
+    return build_host_probe(tmp_path_factory.mktemp("math_contract"), "contract")
 
 
 def ulp_err(a, ref):
@@ -174,6 +231,51 @@ def test_residual_sincos_accuracy(probe, col=9, lim=4e-3):
     c = np.fma(-s0, sd, np.fma(c0, cm, c0)) if hasattr(np, "fma") else c0 + (c0 * cm - s0 * sd)
     assert np.max(np.abs(s - np.sin(a + d))) <= 3.4e-16
     assert np.max(np.abs(c - np.cos(a + d))) <= 3.4e-16
+
+
+def test_tiny_sincos_and_rotate_cm(probe):
+    """tiny_sincos (|d| <= kAdvanceAngle: the carried attitude trig's residual
+    rotation), which returns sin d and cos d - 1, and rotate_cm itself."""
+    lim = 1e-4
+    rng = np.random.default_rng(21)
+    d = np.concatenate([rng.uniform(-lim, lim, 200000), [0.0, -0.0, 1e-12, 1e-300, lim, -lim]])
+    out = probe(d)
+    sd, cm = out[:, 11], out[:, 12]
+    assert np.max(ulp_err(sd, np.sin(d))[np.abs(d) > 1e-300]) <= 1.0
+    assert sd[200000] == 0.0 and sd[200003] == 1e-300
+    cm_ref = -2.0 * np.sin(0.5 * d) ** 2  # cos d - 1 without cancellation
+    # cos d - 1 is truncated (d^4 / 4!): absolute error, what the rotation sees
+    assert np.max(np.abs(cm - cm_ref) - 2 * np.spacing(np.abs(cm_ref))) <= 4.2e-18
+    a = rng.uniform(-np.pi / 3, np.pi / 3, d.size)
+    base = probe(a)
+    rot = probe(np.stack([base[:, 5], base[:, 6], sd, cm], axis=1), rotate=True)
+    assert np.max(np.abs(rot[:, 0] - np.sin(a + d))) <= 3.4e-16
+    assert np.max(np.abs(rot[:, 1] - np.cos(a + d))) <= 3.4e-16
+
+
+@pytest.mark.parametrize("test", [
+    test_sincos_accuracy, test_small_angle_sincos_and_rotation, test_sincos_nonfinite,
+    test_angle_wrap_bit_identical_to_numpy, test_tilt_sincos_accuracy, test_rate_sincos_accuracy,
+    test_residual_sincos_accuracy, test_tiny_sincos_and_rotate_cm], ids=lambda t: t.__name__[5:])
+def test_with_device_contraction(test, probe_contract):
+    """Every test above again, same inputs and bounds, on the host build that
+    rounds as the device code does (HOST_BUILDS "contract").  The tests keep
+    their names for the "separate" build; these are the second compiler."""
+    test(probe_contract)
+
+
+def test_host_builds_differ_for_fast_sincos(tmp_path):
+    """Why every accuracy test above runs on two host builds: with the
+    library's contraction rule sincos_kernel's r + v * (kS1 + z * ps) and its
+    like are fused, and fast_sincos returns other bits for a share of its
+    arguments.  py_mod_2pi (selects and exact subtractions) does not change."""
+    rng = np.random.default_rng(0)
+    x = np.concatenate([rng.uniform(-np.pi - 0.2, np.pi + 0.2, 200000), rng.uniform(-2000.0, 2000.0, 100000)])
+    sep, con = (build_host_probe(tmp_path, b)(x) for b in HOST_BUILDS)
+    share_s, share_c = np.mean(sep[:, 0] != con[:, 0]), np.mean(sep[:, 1] != con[:, 1])
+    print(f"fast_sincos bits differing between the host builds: sin {share_s:.4%} cos {share_c:.4%}")
+    assert share_s > 0 and share_c > 0
+    np.testing.assert_array_equal(sep[:, 2], con[:, 2])
 
 
 CR_SRC = r"""
@@ -321,13 +423,6 @@ int main(int argc, char** argv) {
 """
 
 
-def _host_has_fma():
-    try:
-        return " fma " in open("/proc/cpuinfo").read().replace("\n", " ")
-    except OSError:
-        return False
-
-
 @pytest.fixture(scope="module")
 def glibc_probe(tmp_path_factory):
     if not _host_has_fma():
@@ -359,10 +454,9 @@ def test_glibc_sin_cos_pow2_bitwise_vs_host_libm(glibc_probe):
     assert (bs, bc, bp) == (0, 0, 0)
 
 
-def test_glibc_edge_arguments(glibc_probe):
-    """Branch boundaries (2^-27, 2^-26, 0.126, 0.855469, 2.426265, 105414350),
-    multiples of pi/4 and pi/2 (quadrant edges), the table grid i/128 and its
-    midpoints, and pow's special inputs."""
+def glibc_edge_arguments():
+    """The arguments of test_glibc_edge_arguments (also given to the device
+    build, tests/test_gpu_device_math.py)."""
     edges = []
     for b in (2.0 ** -27, 2.0 ** -26, 0.126, 0.85546875, 2.426265, 105414349.0, 1.0, 0.5):
         for v in (b, np.nextafter(b, 0), np.nextafter(b, np.inf)):
@@ -373,6 +467,14 @@ def test_glibc_edge_arguments(glibc_probe):
                         grid, grid + 1 / 256.0, -grid,
                         [0.0, -0.0, 5e-324, -5e-324, 2.2250738585072014e-308, 1.7976931348623157e308,
                          -1.7976931348623157e308, 1e154, 1.4e154, 1e-160, 1e-170, np.inf, -np.inf, np.nan]])
+    return x
+
+
+def test_glibc_edge_arguments(glibc_probe):
+    """Branch boundaries (2^-27, 2^-26, 0.126, 0.855469, 2.426265, 105414350),
+    multiples of pi/4 and pi/2 (quadrant edges), the table grid i/128 and its
+    midpoints, and pow's special inputs."""
+    x = glibc_edge_arguments()
     n, checked, bs, bc, bp = glibc_probe(x=x)
     assert n == x.size and (bs, bc, bp) == (0, 0, 0)
 
