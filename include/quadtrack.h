@@ -665,6 +665,57 @@ int qt_policy_population_rollout(const qt_env_params* env, const qt_policy_popul
                                  const qt_criteria* crit, const qt_batch* batch, qt_state st, int32_t nsteps,
                                  double* rec, void* stream);
 
+/* ---- supervised policy rollout (additive: QT_ABI_VERSION, qt_policy_version
+   and qt_policy_population_version are unchanged, feature detection goes
+   through qt_policy_supervised_version) ----
+   The imitation mode of the reference's trainer (train.py:654-862) as one
+   fused launch: the POLICY flies the episode (qt_policy_rollout's body, bit
+   for bit: state, target, time, accumulators and rec are those of
+   qt_policy_rollout on the same inputs) and at every step of a running
+   episode a classical TEACHER is asked for its command on the same
+   observation (quad position / velocity, target position / velocity, the env
+   time as the observation time, the batch's hover thrust): the controller of
+   qt_compute_action_obs for batch->K / k_cols (6: Riccati-LQR and heuristic
+   LQR, 9: LQI, 3: PID), structured or dense, shared or per episode, bit for
+   bit.  The teacher's integral state lives in st.integ (LQI 3 rows, PID 4 rows
+   with the last observation time, NaN = none) and is carried from launch to
+   launch; a finished episode calls no teacher and updates no integral.  The
+   teacher never influences the flight.  Per stepped step, in this order:
+     loss[e] += sum_i (u_i - (double)(float)s_i)^2   u: the policy's f32 command
+                widened exactly, s: the teacher's FP64 command rounded to f32 as
+                the trainer's label tensor (train.py:687-696); every product and
+                every add rounded on its own, i = 0..3 in order
+     sample   if the episode's step index (acc[QT_ACC_STEPS] before the step)
+              equals its next sample_steps[j][e]: rows 0-17 of sample[j][.][e]
+              = the policy's f32 features, 18-21 = (float)s, 22-25 = (float)u,
+              and the lane moves to slot j + 1.  Slots whose step the episode
+              never reaches are not written (the caller pre-fills them).  A
+              later launch finds its slot from acc[QT_ACC_STEPS] at entry.
+     teacher_rec[s][i][e] = s_i (FP64), s = the step's index in this launch
+   Out of scope: feed-forward teachers, a population form. */
+#define QT_SUP_ROWS 26   /* 18 features, 4 teacher command, 4 policy command (all f32) */
+typedef struct qt_policy_supervision {
+  int32_t samples;              /* S >= 0 sample slots per episode */
+  int32_t pad_;
+  const int32_t* sample_steps;  /* device [S][n], strictly ascending per episode; NULL iff S == 0 */
+  float*  sample;               /* device [S][QT_SUP_ROWS][n]; NULL iff S == 0 */
+  double* loss;                 /* device [n], read and written: += sum_i (u_i - fl32(s_i))^2 per stepped step */
+  double* teacher_rec;          /* optional device [nsteps][4][n]: the teacher's FP64 command of this launch's steps */
+} qt_policy_supervision;
+
+/* 1: this library has qt_policy_supervised_rollout. */
+int qt_policy_supervised_version(void);
+
+/* QT_EINVAL before any launch: qt_policy_rollout's rules; a NULL ctrl, sup,
+   sup->loss or batch->K; k_cols not 3, 6 or 9; ctrl->use_lqi set without
+   k_cols == 9 or the reverse; st.integ NULL with k_cols != 6; samples < 0, or
+   samples > 0 with a NULL sample_steps or sample; a feed-forward teacher
+   (ctrl->feedforward_enabled or batch->ff).  n == 0 or nsteps == 0 returns
+   QT_OK. */
+int qt_policy_supervised_rollout(const qt_env_params* env, const qt_ctrl_params* ctrl, const qt_policy* policy,
+                                 const qt_criteria* crit, const qt_batch* batch, qt_state st, int32_t nsteps,
+                                 const qt_policy_supervision* sup, double* rec, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

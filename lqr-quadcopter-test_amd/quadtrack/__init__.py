@@ -25,10 +25,10 @@ from .controllers import (
 )
 from .env import BatchedQuadcopterEnv, EnvConfig, QuadcopterEnv, TargetMotion
 from .eval import BatchedEvaluator, Evaluator, evaluate_batched, load_controller, run_hyperparameter_sweep
-from .policy import (PolicyPopulation, PopulationResult, evaluate_policy, evaluate_population, run_policy_loop,
-                     run_policy_population)
+from .policy import (PolicyPopulation, PopulationResult, SupervisedResult, evaluate_policy, evaluate_population,
+                     run_policy_loop, run_policy_population, run_policy_supervised)
 from .rollout import RolloutResult, run_closed_loop
-from .train import SearchResult, search_policy
+from .train import ImitationResult, SearchResult, search_policy, train_imitation
 from .utils import EpisodeMetrics, EvaluationSummary, SuccessCriteria, compute_episode_metrics
 
 __version__ = "0.1.0"
@@ -39,4 +39,5 @@ __all__ = ["BaseController", "BatchedLQR", "BatchedPID", "BatchedRiccatiLQR", "L
            "load_controller", "run_hyperparameter_sweep", "RolloutResult", "run_closed_loop", "EpisodeMetrics", "EvaluationSummary",
            "SuccessCriteria", "compute_episode_metrics", "_abi", "BatchedDeepPolicy", "DeepTrackingPolicy",
            "run_policy_loop", "evaluate_policy", "PolicyPopulation", "PopulationResult", "run_policy_population",
-           "evaluate_population", "search_policy", "SearchResult"]
+           "evaluate_population", "search_policy", "SearchResult", "run_policy_supervised", "SupervisedResult",
+           "train_imitation", "ImitationResult"]

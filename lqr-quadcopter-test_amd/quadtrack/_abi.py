@@ -105,6 +105,13 @@ class PolicyPopulation(C.Structure):
                 ("episodes_per_member", C.c_int64)]
 
 
+class PolicySupervision(C.Structure):
+    """qt_policy_supervision (additive; qt_policy_supervised_version)"""
+
+    _fields_ = [("samples", C.c_int32), ("pad_", C.c_int32), ("sample_steps", C.c_void_p), ("sample", C.c_void_p),
+                ("loss", C.c_void_p), ("teacher_rec", C.c_void_p)]
+
+
 class PolicyObs(C.Structure):
     """qt_policy_obs"""
 
@@ -116,6 +123,8 @@ ACTIVATIONS = ("relu", "tanh", "elu", "leaky_relu")
 POLICY_MAX_HIDDEN, POLICY_MAX_WIDTH, POLICY_INPUTS = 4, 128, 18
 POLICY_VERSION = 1
 POLICY_POPULATION_VERSION = 1
+POLICY_SUPERVISED_VERSION = 1
+SUP_ROWS = 26  # QT_SUP_ROWS: 18 features, 4 teacher command, 4 policy command
 
 
 def policy_block_floats(n_hidden: int, nt: int) -> int:
@@ -151,7 +160,8 @@ EXPORTS = ("qt_abi_version", "qt_host_alloc", "qt_host_free", "qt_stream_sync", 
            "qt_summary_parts", "qt_summary_numpy", "qt_stream_uniform", "qt_frame_reset", "qt_frame_step",
            "qt_compute_action_obs", "qt_frame_closed_step", "qt_lean_reset", "qt_lean_closed_step", "qt_lean_step",
            "qt_lean_expand", "qt_policy_version", "qt_policy_action", "qt_policy_rollout",
-           "qt_policy_population_version", "qt_policy_population_rollout")
+           "qt_policy_population_version", "qt_policy_population_rollout", "qt_policy_supervised_version",
+           "qt_policy_supervised_rollout")
 
 _lib = None
 
@@ -208,6 +218,9 @@ def load():
     L.qt_policy_population_version.argtypes = []
     L.qt_policy_population_rollout.argtypes = [P(EnvParams), P(PolicyPopulation), P(Criteria), P(Batch), State, i32,
                                                vp, vp]
+    L.qt_policy_supervised_version.argtypes = []
+    L.qt_policy_supervised_rollout.argtypes = [P(EnvParams), P(CtrlParams), P(Policy), P(Criteria), P(Batch), State,
+                                               i32, P(PolicySupervision), vp, vp]
     for name in EXPORTS[1:]:
         getattr(L, name).restype = C.c_int
     v = L.qt_abi_version()
@@ -215,6 +228,11 @@ def load():
         raise ImportError(f"libquadtrack ABI {v} != expected {ABI_VERSION}")
     _lib = L
     return L
+
+
+def has_policy_supervised() -> bool:
+    """The loaded library has qt_policy_supervised_rollout in this package's version."""
+    return load().qt_policy_supervised_version() == POLICY_SUPERVISED_VERSION
 
 
 def require_gpu(device=None) -> torch.device:

@@ -236,6 +236,55 @@ class BatchedDeepPolicy:
                                                 C.byref(batch.c_batch(with_k=False)), st.c_state(), int(nsteps),
                                                 _abi.ptr(rec), _abi.stream_of(self.device)), "qt_policy_rollout")
 
+    def rollout_supervised(self, env, ctrl, crit, batch, st, nsteps: int, loss: torch.Tensor,
+                           sample_steps: torch.Tensor | None = None, sample: torch.Tensor | None = None,
+                           rec: torch.Tensor | None = None, teacher_rec: torch.Tensor | None = None) -> None:
+        """qt_policy_supervised_rollout (in place; chunks allowed): the policy
+        flies, the classical teacher of `batch`'s gains and `ctrl` labels every
+        visited state.
+
+        loss          [n] float64, accumulated: sum of squared (policy - f32 teacher) command differences
+        sample_steps  [S, n] int32, strictly ascending per episode (or None: no samples)
+        sample        [S, 26, n] float32, written where an episode reaches its slot's step
+        rec           [nsteps, 16, n] float64 as rollout's
+        teacher_rec   [nsteps, 4, n] float64: the teacher's command of this launch's steps"""
+        if batch.order is not None:
+            raise ValueError("the policy rollout runs episodes in index order (order must be None)")
+        if batch.device != self.device:
+            raise ValueError(f"the batch is on {batch.device}, the policy on {self.device}")
+        n = batch.n
+
+        def want(t, name, numel, dtype):
+            if t.device != self.device or t.dtype != dtype or t.numel() < numel or not t.is_contiguous():
+                raise ValueError(f"{name} must hold {numel} contiguous {dtype} values on {self.device}")
+
+        want(loss, "loss", n, F64)
+        if rec is not None:
+            want(rec, "rec", nsteps * 16 * n, F64)
+        if teacher_rec is not None:
+            want(teacher_rec, "teacher_rec", nsteps * 4 * n, F64)
+        sup = _abi.PolicySupervision()
+        if (sample_steps is None) != (sample is None):
+            raise ValueError("sample_steps and sample go together")
+        if sample_steps is not None:
+            if sample_steps.dim() != 2 or sample_steps.shape[1] != n:
+                raise ValueError(f"sample_steps must be [S, {n}]")
+            S = sample_steps.shape[0]
+            want(sample_steps, "sample_steps", S * n, torch.int32)
+            want(sample, "sample", S * _abi.SUP_ROWS * n, torch.float32)
+            if S:
+                sup.samples, sup.sample_steps, sup.sample = S, sample_steps.data_ptr(), sample.data_ptr()
+        sup.loss = loss.data_ptr()
+        sup.teacher_rec = None if teacher_rec is None else teacher_rec.data_ptr()
+        lib = _abi.load()
+        if not _abi.has_policy_supervised():
+            raise ImportError("libquadtrack has another supervised-rollout ABI than this package")
+        with torch.cuda.device(self.device):
+            check(lib.qt_policy_supervised_rollout(C.byref(env), C.byref(ctrl), self._ref, C.byref(crit),
+                                                   C.byref(batch.c_batch()), st.c_state(), int(nsteps), C.byref(sup),
+                                                   _abi.ptr(rec), _abi.stream_of(self.device)),
+                  "qt_policy_supervised_rollout")
+
 
 def load_checkpoint_file(path) -> dict:
     path = Path(path)
@@ -282,8 +331,14 @@ class DeepTrackingPolicy(BaseController):
     gives the reference's weights) or come from a reference-format checkpoint.
     compute_action runs the network on the GPU (qt_policy_action with n = 1).
 
-    Out of scope: to_onnx, train_mode, get_parameters and training as a whole
-    (the weights come from the reference's trainer through a checkpoint)."""
+    Training: quadtrack.train.train_imitation fits self.network to a classical
+    supervisor's commands (the reference trainer's imitation mode) on the
+    supervised rollout, with torch autograd, and leaves the weights here;
+    quadtrack.train.search_policy is the gradient-free search.  Weights may
+    also come from the reference's trainer through a checkpoint.
+
+    Out of scope: to_onnx, train_mode, get_parameters, and the trainer's other
+    modes (tracking / reward_weighted losses, curriculum, diagnostics)."""
 
     def __init__(self, config: dict | None = None, device: str | None = None):
         super().__init__(name="deep_tracking", config=config)

@@ -10,6 +10,11 @@ one kernel) in place of the classical controllers' rollout.
 (`PolicyPopulation`) in one launch, each member on its own episodes
 (`qt_policy_population_rollout`, csrc/qt_policy_population.hip): the batch
 evaluator of gradient-free search (`quadtrack.train.search_policy`).
+
+`run_policy_supervised` flies the policy while a classical teacher labels
+every visited state (`qt_policy_supervised_rollout`,
+csrc/qt_policy_supervised.hip): the data source of imitation training
+(`quadtrack.train.train_imitation`).
 """
 
 from __future__ import annotations
@@ -29,7 +34,8 @@ from .utils.metrics import EvaluationSummary, SuccessCriteria
 
 __all__ = ["BatchedDeepPolicy", "DeepTrackingPolicy", "run_policy_loop", "evaluate_policy", "policy_batch",
            "pack_params", "policy_tiles", "extract_features", "PolicyPopulation", "PopulationResult", "pack_index",
-           "run_policy_population", "evaluate_population"]
+           "run_policy_population", "evaluate_population", "run_policy_supervised", "SupervisedResult",
+           "sample_steps"]
 
 
 class _NoGains:
@@ -115,6 +121,143 @@ def evaluate_policy(policy, env_config=None, num_episodes: int = 10, base_seed: 
     if with_episode_metrics:
         summary.episode_metrics = res.episode_metrics()
     return summary
+
+
+# ------------------------------------------------------------------ supervised rollout
+
+def sample_steps(n: int, S: int, horizon: int, seed: int = 0) -> np.ndarray:
+    """int32 [S, n]: the step indices at which each of n episodes fills its S
+    sample slots.  Slot j is drawn uniformly from the stratum
+    [floor(j H / S), floor((j + 1) H / S)) of the horizon H with
+    np.random.default_rng(seed) (one [S, n] block of uniforms), so an
+    episode's steps are ascending and distinct by construction and the result
+    is a function of the four arguments only.  S > H is refused (a stratum
+    would be empty).
+
+    The reference's trainer draws an unseeded np.random.choice over the
+    REALISED episode length after the episode (train.py:756-757).  Here the
+    steps are fixed before the launch, over the horizon: an episode that ends
+    early leaves its later slots unfilled (SupervisedResult.valid), and a run
+    is reproducible from its seed."""
+    n, S, H = int(n), int(S), int(horizon)
+    if n < 0 or S < 0 or H < 0:
+        raise ValueError(f"n, S and horizon must be >= 0, got {n}, {S}, {H}")
+    if S > H:
+        raise ValueError(f"{S} sample slots do not fit a horizon of {H} steps")
+    j = np.arange(S, dtype=np.int64)
+    lo, hi = j * H // max(S, 1), (j + 1) * H // max(S, 1)
+    r = np.random.default_rng(seed).random((S, n))
+    k = np.minimum(np.floor(r * (hi - lo)[:, None]).astype(np.int64), (hi - lo - 1)[:, None])
+    return (lo[:, None] + k).astype(np.int32)
+
+
+@dataclass
+class SupervisedResult(RolloutResult):
+    """A supervised run: run_policy_loop's result (the flight is the policy's,
+    bit for bit) plus the teacher's labels."""
+
+    loss: torch.Tensor | None = None            # [n] float64: sum over the flown steps of |u - fl32(s)|^2
+    sample: torch.Tensor | None = None          # [S, 26, n] float32, NaN where a slot was not reached
+    steps_sampled: torch.Tensor | None = None   # [S, n] int32: the slots' step indices (sample_steps)
+    teacher_record: torch.Tensor | None = None  # [steps, 4, n] float64: the teacher's command at every step
+    supervisor: object = None
+
+    @property
+    def features(self) -> torch.Tensor:
+        """[S, n, 18] float32 view: the policy's input at the sampled steps."""
+        return self.sample[:, :18].permute(0, 2, 1)
+
+    @property
+    def targets(self) -> torch.Tensor:
+        """[S, n, 4] float32 view: the teacher's command, the imitation label."""
+        return self.sample[:, 18:22].permute(0, 2, 1)
+
+    @property
+    def commands(self) -> torch.Tensor:
+        """[S, n, 4] float32 view: the policy's own command at the sampled steps."""
+        return self.sample[:, 22:26].permute(0, 2, 1)
+
+    @property
+    def valid(self) -> torch.Tensor:
+        """[S, n] bool: the episode reached the slot's step (sample_steps < steps)."""
+        return self.steps_sampled.to(F64) < self.state.acc[_abi.ACC_STEPS][None, :]
+
+    def dataset(self):
+        """(features [m, 18], targets [m, 4]): the valid pairs, compact, on the device."""
+        v = self.valid
+        return self.features[v], self.targets[v]
+
+    def imitation_loss(self) -> torch.Tensor:
+        """[n] float64: loss / (4 steps), the F.mse_loss of the episode's f32
+        policy commands against its f32 labels over the WHOLE flown episode."""
+        return self.loss / (4.0 * self.state.acc[_abi.ACC_STEPS])
+
+
+def _as_supervisor(supervisor, config, device):
+    if isinstance(supervisor, str):
+        from .controllers import batched_controller
+
+        return batched_controller(supervisor, config, device=device)
+    if not all(hasattr(supervisor, k) for k in ("K", "k_cols", "ctrl", "per_episode")):
+        raise TypeError(f"expected a BatchedRiccatiLQR, BatchedLQR or BatchedPID (or a controller type name), "
+                        f"got {type(supervisor).__name__}")
+    return supervisor
+
+
+def run_policy_supervised(policy, supervisor="riccati_lqr", env_config=None, n: int | None = None, seeds=None,
+                          motion=None, plant_mass=None, criteria=None, draws=None, max_steps: int | None = None,
+                          chunk: int | None = None, record: bool = False, samples_per_episode: int = 32,
+                          sample_seed: int = 0, teacher_record: bool = False,
+                          supervisor_config: dict | None = None) -> SupervisedResult:
+    """run_policy_loop with a classical teacher labelling every visited state
+    (qt_policy_supervised_rollout, csrc/qt_policy_supervised.hip): the policy
+    flies, the supervisor is asked what it would have commanded on the same
+    observation, and the launch keeps the per-episode imitation loss and
+    `samples_per_episode` (features, teacher command) pairs per episode.
+
+    supervisor  a BatchedRiccatiLQR / BatchedLQR / BatchedPID (shared or
+                per-episode gains), or a controller type name with
+                supervisor_config (controllers.batched_controller).  A fresh
+                supervisor per episode (integral zeroed at reset, train.py:669).
+                Feed-forward supervisors are out of scope (ValueError).
+    samples_per_episode, sample_seed  the slots' steps: sample_steps(n, S, max_steps, sample_seed)
+    teacher_record  keep the teacher's FP64 command of every step ([steps, 4, n])
+    The other arguments and the flight itself are run_policy_loop's."""
+    policy = _as_batched(policy)
+    sup = _as_supervisor(supervisor, supervisor_config, policy.device)
+    if sup.ctrl.feedforward_enabled or getattr(sup, "ff", None) is not None:
+        raise ValueError("feed-forward supervisors are out of scope of the supervised rollout")
+    cfg = as_env_config(env_config)
+    env = cfg.to_params()
+    if n is None:
+        n = sup.num_problems if sup.per_episode else (len(seeds) if seeds is not None else 1)
+    batch = build_batch(sup, cfg, n, seeds=seeds, motion=motion, plant_mass=plant_mass, draws=draws,
+                        device=policy.device, group_motion=False)
+    crit = _criteria(criteria)
+    st = core.RolloutState.empty(n, batch.device)
+    core.validate(batch, st)
+    total = max_steps if max_steps is not None else max_steps_for(env)
+    step = chunk or total
+    dev = batch.device
+    S = int(samples_per_episode)
+    steps_dev = torch.as_tensor(sample_steps(n, S, total, sample_seed), device=dev)
+    nan = float("nan")
+    sample = torch.full((S, _abi.SUP_ROWS, n), nan, dtype=torch.float32, device=dev)
+    loss = torch.zeros(n, dtype=F64, device=dev)
+    rec = torch.full((total, 16, n), nan, dtype=F64, device=dev) if record else None
+    trec = torch.full((total, 4, n), nan, dtype=F64, device=dev) if teacher_record else None
+    core.reset(env, batch, st)  # the teacher's integral rows too (PID: no previous observation time)
+    done = 0
+    while done < total:
+        k = min(step, total - done)
+        policy.rollout_supervised(env, sup.ctrl, crit, batch, st, k, loss, steps_dev if S else None,
+                                  sample if S else None, None if rec is None else rec[done:done + k],
+                                  None if trec is None else trec[done:done + k])
+        done += k
+    met = core.episode_metrics(crit, st)
+    return SupervisedResult(metrics=met, state=st, batch=batch, criteria=crit, record=rec, env=env, ctrl=sup.ctrl,
+                            policy=policy, loss=loss, sample=sample, steps_sampled=steps_dev, teacher_record=trec,
+                            supervisor=sup)
 
 
 # ------------------------------------------------------------------ populations

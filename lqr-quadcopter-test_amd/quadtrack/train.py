@@ -16,10 +16,13 @@ per episode) and the three means are numpy's, bit for bit, from the
 block-pairwise summary kernel (`qt_summary_numpy`).  The env is built as the
 Trainer builds it (train.py:306-312): EnvConfig defaults with the
 TrainingConfig's seed, episode length, motion type and target radius.
-Deep-policy training by gradient (the rest of train.py) is outside the hot
-path.  `search_policy` is a gradient-free counterpart on the population
-rollout: evolution strategies over a policy's flat weight vector, one fused
-launch of every candidate per generation.
+`train_imitation` is the trainer's imitation mode (train.py:654-862) on the
+supervised rollout: per epoch one fused launch in which the policy flies and a
+classical supervisor labels every visited state, then torch autograd on the
+sampled (features, label) pairs.  The trainer's other modes are out of scope.
+`search_policy` is a gradient-free counterpart on the population rollout:
+evolution strategies over a policy's flat weight vector, one fused launch of
+every candidate per generation.
 """
 
 from __future__ import annotations
@@ -118,6 +121,142 @@ def evaluate_epoch(config=None, epoch: int = 0, *, controller: str = "riccati_lq
     return EpochResult(mean_reward=mean_reward, mean_on_target_ratio=mean_ratio, mean_tracking_error=mean_err,
                        difficulty=1.0, episode_reward=reward[0].clone(), episode_on_target_ratio=ratio,
                        episode_tracking_error=reward[1].clone(), episode_steps=steps.to(torch.int64))
+
+
+# ------------------------------------------------------------------ imitation training
+
+@dataclass
+class ImitationResult:
+    """train_imitation's history (host tensors, one entry per epoch) and the trained weights."""
+
+    mean_reward: torch.Tensor            # [E] the three means of _train_epoch's dict (train.py:737-749)
+    mean_on_target_ratio: torch.Tensor   # [E]
+    mean_tracking_error: torch.Tensor    # [E]
+    imitation_loss: torch.Tensor         # [E] mean over the episodes of SupervisedResult.imitation_loss()
+    dataset_loss_before: torch.Tensor    # [E] imitation_weight * mse over the epoch's data set, before its updates
+    dataset_loss_after: torch.Tensor     # [E] the same after them
+    dataset_size: torch.Tensor           # [E] int64 valid (features, target) pairs
+    state_dict: dict                     # the final weights (host), also loaded into policy.network
+    policy: object                       # the DeepTrackingPolicy that was trained
+    datasets: list | None = None         # keep_datasets: per epoch (features [m, 18], targets [m, 4]) on the device
+
+
+def _make_optimizer(name: str, params, learning_rate: float, weight_decay: float):
+    """Trainer._create_optimizer (train.py:476-500)."""
+    name = name.lower()
+    if name == "adam":
+        return torch.optim.Adam(params, lr=learning_rate, weight_decay=weight_decay)
+    if name == "sgd":
+        return torch.optim.SGD(params, lr=learning_rate, weight_decay=weight_decay, momentum=0.9)
+    if name == "adamw":
+        return torch.optim.AdamW(params, lr=learning_rate, weight_decay=weight_decay)
+    raise ValueError(f"Unknown optimizer: {name}")
+
+
+def train_imitation(policy, supervisor="riccati_lqr", supervisor_config: dict | None = None, env_config=None, *,
+                    epochs: int, episodes_per_epoch: int, samples_per_episode: int = 32, batch_size: int = 256,
+                    learning_rate: float = 1e-3, optimizer: str = "adam", grad_clip: float = 1.0,
+                    imitation_weight: float = 1.0, weight_decay: float = 0.0, env_seed: int = 42, seed: int = 0,
+                    max_steps: int | None = None, motion=None, keep_datasets: bool = False,
+                    device=None) -> ImitationResult:
+    """Imitation training of a DeepTrackingPolicy on the supervised rollout
+    (the imitation mode of the reference's trainer, train.py:654-862).
+
+    Per epoch e: ONE fused launch (policy.run_policy_supervised) flies
+    `episodes_per_epoch` episodes of the current policy on the trainer's reset
+    seeds env_seed + e * 1000 + j (train.py:662) while the supervisor labels
+    every visited state, and keeps `samples_per_episode` (features, teacher
+    command) pairs per episode at the steps sample_steps(..., seed + e).  Then
+    minibatch steps of torch autograd (one pass over the epoch's data set in a
+    seeded random order, `batch_size` pairs per step) minimise
+    imitation_weight * F.mse_loss(net(features), targets), with the trainer's
+    optimisers (train.py:476-500) and clip_grad_norm_ (train.py:831-834;
+    grad_clip <= 0: none).  The forward pass is policy.network's own modules
+    followed by the sigmoid / output-bounds stage; the new weights are packed
+    again for the next epoch's launch and stay in policy.network.
+
+    The reference updates once per EPISODE from an unseeded sample of that
+    episode's steps; here the update follows the epoch's launch and its order
+    is a function of `seed`.  mean_reward is the epoch mean of minus the sum of
+    an episode's post-step tracking errors, formed from the rollout's
+    accumulators (sum of pre-step errors - the first + the last post-step one).
+
+    Out of scope: the tracking and control-effort terms of utils/losses.py
+    (tracking_weight is taken as 0), curriculum, diagnostics, NaN recovery,
+    checkpoint cadence, the reward_weighted mode, a HIP backward pass (the
+    gradient is torch's) and a population form."""
+    from .controllers.deep import DeepTrackingPolicy, _bounds
+    from .policy import _as_supervisor, run_policy_supervised
+
+    if not isinstance(policy, DeepTrackingPolicy):
+        raise TypeError(f"expected a DeepTrackingPolicy, got {type(policy).__name__}")
+    if epochs < 1 or episodes_per_epoch < 1 or batch_size < 1 or samples_per_episode < 1:
+        raise ValueError("epochs, episodes_per_epoch, samples_per_episode and batch_size must be >= 1")
+    net = policy.network
+    opt_probe = _make_optimizer(optimizer, [torch.nn.Parameter(torch.zeros(1))], learning_rate, weight_decay)
+    del opt_probe  # an unknown optimizer is refused before any GPU work
+    dev = _abi.require_gpu(device if device is not None else (policy.device if policy.device.type == "cuda" else None))
+    sup = _as_supervisor(supervisor, supervisor_config, dev)
+    home = next(net.parameters()).device
+    net.to(dev)
+    opt = _make_optimizer(optimizer, list(net.parameters()), learning_rate, weight_decay)
+    _, lo, hi = _bounds(net.output_bounds)
+    scale = torch.tensor([h - l for l, h in zip(lo, hi)], dtype=torch.float32, device=dev)  # (float)(hi - lo)
+    low = torch.tensor(lo, dtype=torch.float32, device=dev)
+
+    def forward(f):  # PolicyNetwork.forward (deep_tracking_policy.py): sigmoid(raw) * (hi - lo) + lo
+        return torch.sigmoid(net.output_layer(net.feature_extractor(f))) * scale + low
+
+    def mse(f, y):
+        return imitation_weight * torch.nn.functional.mse_loss(forward(f), y)
+
+    hist = {k: [] for k in ("reward", "ratio", "err", "imit", "before", "after", "size")}
+    datasets = [] if keep_datasets else None
+    gen = torch.Generator(device=dev)
+    try:
+        for e in range(epochs):
+            E = int(episodes_per_epoch)
+            res = run_policy_supervised(policy.to_batched(dev), sup, env_config, n=E,
+                                        seeds=generation_seeds(env_seed, e, E), motion=motion, max_steps=max_steps,
+                                        samples_per_episode=samples_per_episode, sample_seed=seed + e)
+            st = res.state
+            steps = st.acc[_abi.ACC_STEPS]
+            d = st.x[0:3] - st.target[0:3]
+            last = torch.sqrt((d * d).sum(dim=0))  # the last step's info["tracking_error"]
+            first = torch.sqrt((res.batch.offset * res.batch.offset).sum(dim=0))
+            hist["reward"].append(-(st.acc[_abi.ACC_SUM_ERR] - first + last).mean())
+            hist["ratio"].append((st.acc[_abi.ACC_ON_POST] / steps).mean())
+            hist["err"].append(last.mean())
+            hist["imit"].append(res.imitation_loss().mean())
+            feats, targets = res.dataset()
+            if keep_datasets:
+                datasets.append((feats, targets))
+            m = feats.shape[0]
+            hist["size"].append(torch.tensor(m))
+            with torch.no_grad():
+                hist["before"].append(mse(feats, targets).to(torch.float64))
+            gen.manual_seed(int(seed) + e)
+            order = torch.randperm(m, generator=gen, device=dev)
+            for k in range(0, m, int(batch_size)):
+                idx = order[k:k + int(batch_size)]
+                loss = mse(feats.index_select(0, idx), targets.index_select(0, idx))
+                opt.zero_grad()
+                loss.backward()
+                if grad_clip > 0:
+                    torch.nn.utils.clip_grad_norm_(net.parameters(), grad_clip)
+                opt.step()
+            with torch.no_grad():
+                hist["after"].append(mse(feats, targets).to(torch.float64))
+    finally:
+        net.to(home)
+    policy._batched = None  # compute_action packs the new weights
+    stack = lambda k: torch.stack([v.detach().cpu() for v in hist[k]])  # noqa: E731
+    return ImitationResult(mean_reward=stack("reward"), mean_on_target_ratio=stack("ratio"),
+                           mean_tracking_error=stack("err"), imitation_loss=stack("imit"),
+                           dataset_loss_before=stack("before"), dataset_loss_after=stack("after"),
+                           dataset_size=stack("size"),
+                           state_dict={k: v.detach().cpu().clone() for k, v in net.state_dict().items()},
+                           policy=policy, datasets=datasets)
 
 
 # ------------------------------------------------------------------ policy search

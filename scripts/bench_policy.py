@@ -22,6 +22,13 @@
       (b) the per-member way: K members' single-policy launches, scaled by
       members / K.  HIP events, best of --passes.
 
+  python scripts/bench_policy.py --supervised [--episodes 65536] [--steps 300] [--samples 32] [--passes 10]
+      The supervised rollout (Riccati-LQR teacher): (a) one
+      qt_policy_supervised_rollout launch, (c) qt_policy_rollout on the same
+      inputs (the floor), both by HIP events, best of --passes, and (b) the
+      per-step way to the same labels (policy action + teacher action +
+      env.step, three launches per step), by the wall clock, best of 3.
+
 Each run prints one JSON line and appends it to --out when given.
 """
 
@@ -188,6 +195,74 @@ def population(args):
     return line
 
 
+def supervised(args):
+    """(a) one qt_policy_supervised_rollout launch (Riccati-LQR teacher, --samples slots per episode);
+    (c) qt_policy_rollout on the same inputs, the floor; (b) the way to the same labels without the
+    supervised kernel: BatchedDeepPolicy.compute_action + BatchedRiccatiLQR.compute_action + env.step, one
+    step at a time, by the wall clock between two synchronisations (best of 3, as --baseline)."""
+    import quadtrack
+    from quadtrack import core
+    from quadtrack.controllers import BatchedRiccatiLQR
+    from quadtrack.env.config import as_env_config
+    from quadtrack.policy import sample_steps
+    from quadtrack.rollout import build_batch
+
+    dev = torch.device("cuda:0")
+    net = network("cpu", args.hidden)
+    sd = {}
+    for i in range(len(args.hidden)):
+        sd[f"feature_extractor.{2 * i}.weight"], sd[f"feature_extractor.{2 * i}.bias"] = net[2 * i].weight, net[2 * i].bias
+    sd["output_layer.weight"], sd["output_layer.bias"] = net[-1].weight, net[-1].bias
+    pol = quadtrack.BatchedDeepPolicy.from_state_dict(sd, args.hidden, "relu", device=dev)
+    sup = BatchedRiccatiLQR({"dt": 0.01}, device=dev)
+    cfg = as_env_config(ENV_CFG)
+    env, crit, n, S = cfg.to_params(), core.criteria(), args.episodes, args.samples
+    batch = build_batch(sup, cfg, n, seeds=np.arange(n), group_motion=False)
+    st = core.RolloutState.empty(n, dev)
+    steps = torch.as_tensor(sample_steps(n, S, args.steps, 0), device=dev)
+    sample = torch.empty(S, quadtrack._abi.SUP_ROWS, n, dtype=torch.float32, device=dev)
+    loss = torch.zeros(n, dtype=torch.float64, device=dev)
+
+    def reset():
+        core.reset(env, batch, st)
+        loss.zero_()
+        sample.fill_(float("nan"))
+
+    a_best, a_all = _event_ms(lambda: pol.rollout_supervised(env, sup.ctrl, crit, batch, st, args.steps, loss, steps,
+                                                             sample), reset, args.passes)
+    a_steps = float(st.acc[quadtrack._abi.ACC_STEPS].sum())
+    mse = float((loss / (4.0 * st.acc[quadtrack._abi.ACC_STEPS])).mean())
+    filled = float((~torch.isnan(sample[:, 0])).double().mean())
+    c_best, c_all = _event_ms(lambda: pol.rollout(env, crit, batch, st, args.steps), reset, args.passes)
+    c_steps = float(st.acc[quadtrack._abi.ACC_STEPS].sum())
+    benv = quadtrack.BatchedQuadcopterEnv(n, ENV_CFG, device=dev)
+    walls = []
+    for _ in range(4):  # the first pass warms up
+        obs = benv.reset(np.arange(n))
+        sup.reset(n)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.steps):
+            act = pol.compute_action(obs)
+            sup.compute_action(obs)  # the label of this step (a caller would keep it)
+            obs, _, _, _ = benv.step(act)
+        torch.cuda.synchronize()
+        walls.append((time.perf_counter() - t0) * 1e3)
+    b_best = min(walls[1:])
+    return {"what": "policy_supervised", "network": f"{list(args.hidden)} relu", "teacher": "riccati_lqr dt 0.01",
+            "episodes": n, "steps": args.steps, "samples_per_episode": S, "passes": args.passes,
+            "a_supervised_ms_best": a_best, "a_supervised_ms_all": a_all, "a_env_steps": a_steps,
+            "a_ns_per_env_step": a_best * 1e6 / a_steps, "mean_imitation_loss": mse, "sample_slots_filled": filled,
+            "c_policy_rollout_ms_best": c_best, "c_policy_rollout_ms_all": c_all, "c_env_steps": c_steps,
+            "a_over_c": a_best / c_best,
+            "b_per_step_api_wall_ms_best": b_best, "b_per_step_api_wall_ms_all": [round(t, 3) for t in walls[1:]],
+            "a_over_b": a_best / b_best,
+            "b_path": "BatchedDeepPolicy.compute_action + BatchedRiccatiLQR.compute_action + BatchedQuadcopterEnv.step, "
+                      "three launches per step, wall clock between synchronisations, best of 3 (labels only: no "
+                      "loss, no samples kept)",
+            "timer": "HIP events around the rollout launch (reset, loss and sample pre-fill outside) for (a) and (c)"}
+
+
 def baseline(args):
     import quadtrack
 
@@ -233,13 +308,16 @@ def main():
     ap.add_argument("--per-member", type=int, default=64, help="population mode: episodes per member")
     ap.add_argument("--sample", type=int, default=0,
                     help="population mode: members whose single-policy launches are timed and scaled (0: skip)")
+    ap.add_argument("--supervised", action="store_true", help="the supervised rollout against its floor and the per-step way")
+    ap.add_argument("--samples", type=int, default=32, help="supervised mode: sample slots per episode")
     args = ap.parse_args()
     args.hidden = [int(v) for v in args.hidden.split(",")]
     if args.steps is None:
-        args.steps = 300 if args.baseline or args.members else 3000
+        args.steps = 300 if args.baseline or args.members or args.supervised else 3000
     if args.passes is None:
         args.passes = 3 if args.baseline else 10
-    line = population(args) if args.members else baseline(args) if args.baseline else fused(args)
+    line = (supervised(args) if args.supervised else population(args) if args.members
+            else baseline(args) if args.baseline else fused(args))
     line["device"] = torch.cuda.get_device_name(0)
     text = json.dumps(line)
     print(text)
