@@ -716,6 +716,55 @@ int qt_policy_supervised_rollout(const qt_env_params* env, const qt_ctrl_params*
                                  const qt_criteria* crit, const qt_batch* batch, qt_state st, int32_t nsteps,
                                  const qt_policy_supervision* sup, double* rec, void* stream);
 
+/* ---- imitation-loss gradient (additive: QT_ABI_VERSION and the other
+   version functions are unchanged, feature detection goes through
+   qt_policy_grad_version) ----
+   The loss that imitation training minimises and its gradient, on the f32
+   MFMA path of the forward pass (csrc/qt_policy_grad.hpp: layout, summation
+   and reduction order).  For the m samples s with features f_s (18 f32) and
+   label t_s (4 f32):
+     loss = weight / (4 m) * sum_s sum_i (u_i(f_s) - t_{s,i})^2
+   with u = sigmoid(raw) * (float)(hi - lo) + lo the policy's f32 command,
+   bit for bit qt_policy_action's for an observation with those features:
+   imitation_weight * F.mse_loss(net(f), t).  The factor weight * 2 / (4 m) is
+   formed in double, rounded once to f32 and applied to the output layer's
+   delta; the loss is the FP64 sum of the f32 squared errors times
+   weight / (4 m) in double.  grad holds flat-size f32 elements in
+   parameters_to_vector(network.parameters()) order: per layer the weight
+   [out][in] row-major, then the bias; the packed block's padding has no
+   element.  No floating-point atomics: the same inputs give the same bits, in
+   an order that depends on m alone.  Nothing is accumulated into grad, loss
+   or the workspace: their previous contents do not matter.
+   Out of scope: the optimiser step and gradient clipping, a population form,
+   the tracking and control-effort loss terms. */
+typedef struct qt_policy_grad_io {
+  const float* features;   /* device, [rows][18] row-major */
+  const float* targets;    /* device, [rows][4]  row-major */
+  const int64_t* index;    /* device, may be NULL: samples are rows 0..m-1; else m row numbers in [0, rows).
+                              The values are not read on the host: a row number outside [0, rows) is the
+                              caller's error (an out-of-bounds read). */
+  int64_t rows, m;
+  double weight;           /* imitation_weight */
+  float* grad;             /* device, [flat size], parameters_to_vector order */
+  double* loss;            /* device, [1] */
+  float* pred;             /* device, may be NULL: [m][4] the forward commands */
+  void* workspace;         /* device, 8-byte aligned, qt_policy_grad_workspace(policy, m) bytes */
+  int64_t workspace_bytes;
+} qt_policy_grad_io;
+
+/* 1: this library has qt_policy_imitation_grad. */
+int qt_policy_grad_version(void);
+
+/* Bytes of workspace for m samples; < 0: an invalid shape (qt_policy's rules) or m < 1. */
+int64_t qt_policy_grad_workspace(const qt_policy* policy, int64_t m);
+
+/* QT_EINVAL before any launch: a NULL policy, io, features, targets, grad,
+   loss or workspace; an invalid shape (qt_policy's rules); m < 1, rows < 1,
+   or rows < m with a NULL index; workspace_bytes below
+   qt_policy_grad_workspace; a non-finite weight.  Three launches on `stream`,
+   no host synchronisation. */
+int qt_policy_imitation_grad(const qt_policy* policy, const qt_policy_grad_io* io, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -112,6 +112,14 @@ class PolicySupervision(C.Structure):
                 ("loss", C.c_void_p), ("teacher_rec", C.c_void_p)]
 
 
+class PolicyGradIO(C.Structure):
+    """qt_policy_grad_io (additive; qt_policy_grad_version)"""
+
+    _fields_ = [("features", C.c_void_p), ("targets", C.c_void_p), ("index", C.c_void_p), ("rows", C.c_int64),
+                ("m", C.c_int64), ("weight", C.c_double), ("grad", C.c_void_p), ("loss", C.c_void_p),
+                ("pred", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
+
+
 class PolicyObs(C.Structure):
     """qt_policy_obs"""
 
@@ -124,6 +132,7 @@ POLICY_MAX_HIDDEN, POLICY_MAX_WIDTH, POLICY_INPUTS = 4, 128, 18
 POLICY_VERSION = 1
 POLICY_POPULATION_VERSION = 1
 POLICY_SUPERVISED_VERSION = 1
+POLICY_GRAD_VERSION = 1
 SUP_ROWS = 26  # QT_SUP_ROWS: 18 features, 4 teacher command, 4 policy command
 
 
@@ -161,7 +170,7 @@ EXPORTS = ("qt_abi_version", "qt_host_alloc", "qt_host_free", "qt_stream_sync", 
            "qt_compute_action_obs", "qt_frame_closed_step", "qt_lean_reset", "qt_lean_closed_step", "qt_lean_step",
            "qt_lean_expand", "qt_policy_version", "qt_policy_action", "qt_policy_rollout",
            "qt_policy_population_version", "qt_policy_population_rollout", "qt_policy_supervised_version",
-           "qt_policy_supervised_rollout")
+           "qt_policy_supervised_rollout", "qt_policy_grad_version", "qt_policy_imitation_grad")
 
 _lib = None
 
@@ -221,6 +230,10 @@ def load():
     L.qt_policy_supervised_version.argtypes = []
     L.qt_policy_supervised_rollout.argtypes = [P(EnvParams), P(CtrlParams), P(Policy), P(Criteria), P(Batch), State,
                                                i32, P(PolicySupervision), vp, vp]
+    L.qt_policy_grad_version.argtypes = []
+    L.qt_policy_grad_workspace.argtypes = [P(Policy), i64]
+    L.qt_policy_grad_workspace.restype = i64
+    L.qt_policy_imitation_grad.argtypes = [P(Policy), P(PolicyGradIO), vp]
     for name in EXPORTS[1:]:
         getattr(L, name).restype = C.c_int
     v = L.qt_abi_version()
@@ -233,6 +246,11 @@ def load():
 def has_policy_supervised() -> bool:
     """The loaded library has qt_policy_supervised_rollout in this package's version."""
     return load().qt_policy_supervised_version() == POLICY_SUPERVISED_VERSION
+
+
+def has_policy_grad() -> bool:
+    """The loaded library has qt_policy_imitation_grad in this package's version."""
+    return load().qt_policy_grad_version() == POLICY_GRAD_VERSION
 
 
 def require_gpu(device=None) -> torch.device:

@@ -285,6 +285,84 @@ class BatchedDeepPolicy:
                                                    _abi.ptr(rec), _abi.stream_of(self.device)),
                   "qt_policy_supervised_rollout")
 
+    def imitation_gradient(self, features: torch.Tensor, targets: torch.Tensor, index: torch.Tensor | None = None,
+                           weight: float = 1.0, *, grad: torch.Tensor | None = None,
+                           pred: torch.Tensor | None = None):
+        """qt_policy_imitation_grad: the imitation loss
+        weight * F.mse_loss(network(features), targets) of a minibatch and its
+        gradient with respect to every weight and bias, on the forward pass's
+        MFMA path (csrc/qt_policy_grad.hpp).
+
+        features  [rows, 18] float32, contiguous, on the policy's device
+        targets   [rows, 4] float32, contiguous
+        index     None: the samples are rows 0..m-1 with m = rows; or an [m]
+                  int64 tensor of row numbers (not checked: a row number
+                  outside [0, rows) is the caller's error)
+        grad      optional [flat_size] float32 output (parameters_to_vector order)
+        pred      optional [m, 4] float32 output: the forward commands, bit for
+                  bit compute_action's for observations with those features
+        Returns (loss [1] float64, grad [flat_size] float32), both on the
+        device; no host synchronisation.  The workspace is cached per m."""
+        dev = self.device
+
+        def want(t, name, shape, dtype):
+            if not isinstance(t, torch.Tensor):
+                raise TypeError(f"{name} must be a torch.Tensor, got {type(t).__name__}")
+            if t.device != dev:
+                raise ValueError(f"{name} is on {t.device}, the policy on {dev}")
+            if t.dtype != dtype:
+                raise ValueError(f"{name} must be {dtype}, got {t.dtype}")
+            if tuple(t.shape) != tuple(shape):
+                raise ValueError(f"{name} must have shape {list(shape)}, got {list(t.shape)}")
+            if not t.is_contiguous():
+                raise ValueError(f"{name} must be contiguous")
+
+        if not isinstance(features, torch.Tensor) or features.dim() != 2:
+            raise ValueError(f"features must be a [rows, {POLICY_INPUTS}] tensor")
+        rows = features.shape[0]
+        want(features, "features", (rows, POLICY_INPUTS), torch.float32)
+        want(targets, "targets", (rows, 4), torch.float32)
+        if index is None:
+            m = rows
+        else:
+            if not isinstance(index, torch.Tensor) or index.dim() != 1:
+                raise ValueError("index must be a one-dimensional int64 tensor")
+            m = index.shape[0]
+            want(index, "index", (m,), torch.int64)
+        if m < 1 or rows < 1:
+            raise ValueError("the gradient needs at least one sample")
+        weight = float(weight)
+        if not np.isfinite(weight):
+            raise ValueError(f"weight must be finite, got {weight}")
+        size = flat_size(self.hidden_sizes)
+        if grad is None:
+            grad = torch.empty(size, dtype=torch.float32, device=dev)
+        else:
+            want(grad, "grad", (size,), torch.float32)
+        if pred is not None:
+            want(pred, "pred", (m, 4), torch.float32)
+        lib = _abi.load()
+        if not _abi.has_policy_grad():
+            raise ImportError("libquadtrack has another imitation-gradient ABI than this package")
+        cache = self.__dict__.setdefault("_grad_workspace", {})
+        ws = cache.get(m)
+        if ws is None:
+            nbytes = lib.qt_policy_grad_workspace(self._ref, m)
+            if nbytes < 0:
+                raise ValueError(f"no gradient workspace for {m} samples of this policy")
+            ws = cache[m] = torch.empty((nbytes + 7) // 8, dtype=F64, device=dev)
+        loss = torch.empty(1, dtype=F64, device=dev)
+        io = _abi.PolicyGradIO()
+        io.features, io.targets = features.data_ptr(), targets.data_ptr()
+        io.index = None if index is None else index.data_ptr()
+        io.rows, io.m, io.weight = rows, m, weight
+        io.grad, io.loss = grad.data_ptr(), loss.data_ptr()
+        io.pred = None if pred is None else pred.data_ptr()
+        io.workspace, io.workspace_bytes = ws.data_ptr(), ws.numel() * 8
+        with on_device(dev):
+            check(lib.qt_policy_imitation_grad(self._ref, C.byref(io), raw_stream(dev)), "qt_policy_imitation_grad")
+        return loss, grad
+
 
 def load_checkpoint_file(path) -> dict:
     path = Path(path)
@@ -333,7 +411,9 @@ class DeepTrackingPolicy(BaseController):
 
     Training: quadtrack.train.train_imitation fits self.network to a classical
     supervisor's commands (the reference trainer's imitation mode) on the
-    supervised rollout, with torch autograd, and leaves the weights here;
+    supervised rollout, with torch autograd or the HIP backward pass
+    (backend="hip", BatchedDeepPolicy.imitation_gradient), and leaves the
+    weights here;
     quadtrack.train.search_policy is the gradient-free search.  Weights may
     also come from the reference's trainer through a checkpoint.
 

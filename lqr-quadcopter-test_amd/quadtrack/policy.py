@@ -15,6 +15,10 @@ evaluator of gradient-free search (`quadtrack.train.search_policy`).
 every visited state (`qt_policy_supervised_rollout`,
 csrc/qt_policy_supervised.hip): the data source of imitation training
 (`quadtrack.train.train_imitation`).
+
+`imitation_gradient` is that training's loss and gradient on the forward
+pass's MFMA path (`qt_policy_imitation_grad`, csrc/qt_policy_grad.hip): the
+backward pass of `train_imitation(..., backend="hip")`.
 """
 
 from __future__ import annotations
@@ -35,7 +39,7 @@ from .utils.metrics import EvaluationSummary, SuccessCriteria
 __all__ = ["BatchedDeepPolicy", "DeepTrackingPolicy", "run_policy_loop", "evaluate_policy", "policy_batch",
            "pack_params", "policy_tiles", "extract_features", "PolicyPopulation", "PopulationResult", "pack_index",
            "run_policy_population", "evaluate_population", "run_policy_supervised", "SupervisedResult",
-           "sample_steps"]
+           "sample_steps", "imitation_gradient"]
 
 
 class _NoGains:
@@ -69,6 +73,14 @@ def _as_batched(policy) -> BatchedDeepPolicy:
     if not isinstance(policy, BatchedDeepPolicy):
         raise TypeError(f"expected a DeepTrackingPolicy, a BatchedDeepPolicy or a config dict, got {type(policy).__name__}")
     return policy
+
+
+def imitation_gradient(policy, features, targets, index=None, weight: float = 1.0, *, grad=None, pred=None):
+    """BatchedDeepPolicy.imitation_gradient for a BatchedDeepPolicy, a
+    DeepTrackingPolicy or its config dict: (loss [1] float64, grad [flat_size]
+    float32) of weight * F.mse_loss(network(features), targets) on the device
+    (qt_policy_imitation_grad, csrc/qt_policy_grad.hip)."""
+    return _as_batched(policy).imitation_gradient(features, targets, index, weight, grad=grad, pred=pred)
 
 
 def run_policy_loop(policy, env_config=None, n: int | None = None, seeds=None, motion=None, plant_mass=None,

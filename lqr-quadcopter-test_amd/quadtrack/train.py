@@ -18,7 +18,8 @@ Trainer builds it (train.py:306-312): EnvConfig defaults with the
 TrainingConfig's seed, episode length, motion type and target radius.
 `train_imitation` is the trainer's imitation mode (train.py:654-862) on the
 supervised rollout: per epoch one fused launch in which the policy flies and a
-classical supervisor labels every visited state, then torch autograd on the
+classical supervisor labels every visited state, then torch autograd (or, with
+backend="hip", the HIP backward pass of csrc/qt_policy_grad.hip) on the
 sampled (features, label) pairs.  The trainer's other modes are out of scope.
 `search_policy` is a gradient-free counterpart on the population rollout:
 evolution strategies over a policy's flat weight vector, one fused launch of
@@ -158,7 +159,7 @@ def train_imitation(policy, supervisor="riccati_lqr", supervisor_config: dict | 
                     learning_rate: float = 1e-3, optimizer: str = "adam", grad_clip: float = 1.0,
                     imitation_weight: float = 1.0, weight_decay: float = 0.0, env_seed: int = 42, seed: int = 0,
                     max_steps: int | None = None, motion=None, keep_datasets: bool = False,
-                    device=None) -> ImitationResult:
+                    device=None, backend: str = "torch") -> ImitationResult:
     """Imitation training of a DeepTrackingPolicy on the supervised rollout
     (the imitation mode of the reference's trainer, train.py:654-862).
 
@@ -181,15 +182,33 @@ def train_imitation(policy, supervisor="riccati_lqr", supervisor_config: dict | 
     an episode's post-step tracking errors, formed from the rollout's
     accumulators (sum of pre-step errors - the first + the last post-step one).
 
+    backend="torch" (the default) computes loss and gradient with torch's
+    modules and autograd.  backend="hip" computes them with
+    qt_policy_imitation_grad (csrc/qt_policy_grad.hip) on the rollout's own
+    MFMA forward pass, at exactly the commands the rollout flies: per
+    minibatch one device gather of the current parameters into the packed
+    block (pack_index), one call of the gradient entry with the minibatch's
+    index into the epoch's data set (no index_select copies), each
+    parameter's .grad a view of the flat gradient, then the same
+    clip_grad_norm_ and torch optimiser; dataset_loss_before / after come from
+    the same entry over the whole data set.  Nothing in the minibatch loop
+    synchronises with the host.  The epoch's rollout, seeds and sampling are
+    the same under either backend.
+
     Out of scope: the tracking and control-effort terms of utils/losses.py
     (tracking_weight is taken as 0), curriculum, diagnostics, NaN recovery,
-    checkpoint cadence, the reward_weighted mode, a HIP backward pass (the
-    gradient is torch's) and a population form."""
-    from .controllers.deep import DeepTrackingPolicy, _bounds
+    checkpoint cadence, the reward_weighted mode, a fused clip + optimiser
+    kernel (both stay torch's), a population form of the gradient, reading the
+    rollout's [S][26][n] sample block in place (the valid pairs are compacted
+    first), and an exact host model of the gradient's summation order."""
+    from .controllers.deep import (BatchedDeepPolicy, DeepTrackingPolicy, PolicyPopulation, _bounds, flat_size,
+                                   policy_tiles, unflatten)
     from .policy import _as_supervisor, run_policy_supervised
 
     if not isinstance(policy, DeepTrackingPolicy):
         raise TypeError(f"expected a DeepTrackingPolicy, got {type(policy).__name__}")
+    if backend not in ("torch", "hip"):
+        raise ValueError(f"Unknown backend: {backend}. Valid: 'torch', 'hip'")
     if epochs < 1 or episodes_per_epoch < 1 or batch_size < 1 or samples_per_episode < 1:
         raise ValueError("epochs, episodes_per_epoch, samples_per_episode and batch_size must be >= 1")
     net = policy.network
@@ -209,6 +228,26 @@ def train_imitation(policy, supervisor="riccati_lqr", supervisor_config: dict | 
 
     def mse(f, y):
         return imitation_weight * torch.nn.functional.mse_loss(forward(f), y)
+
+    hip = None
+    if backend == "hip":
+        sizes, params = list(net.hidden_sizes), list(net.parameters())
+        gather, _ = PolicyPopulation._device_index(sizes, dev)
+        src = torch.zeros(flat_size(sizes) + 1, dtype=torch.float32, device=dev)  # [theta, the padding's zero]
+        block = torch.empty(_abi.policy_block_floats(len(sizes), policy_tiles(sizes)), dtype=torch.float32, device=dev)
+        flat_grad = torch.zeros(flat_size(sizes), dtype=torch.float32, device=dev)
+        hip = BatchedDeepPolicy.from_block(block, sizes, net.activation_name, net.output_bounds)
+        views = unflatten(flat_grad, sizes)
+        grad_views = [views[name] for name, _ in net.named_parameters()]
+
+        def pack():  # the current parameters into the packed block: one device gather
+            with torch.no_grad():
+                torch.cat([p.reshape(-1) for p in params], out=src[:-1])
+                torch.index_select(src, 0, gather, out=block)
+
+        def hip_loss(f, y):
+            pack()
+            return hip.imitation_gradient(f, y, None, imitation_weight, grad=flat_grad)[0][0]
 
     hist = {k: [] for k in ("reward", "ratio", "err", "imit", "before", "after", "size")}
     datasets = [] if keep_datasets else None
@@ -233,20 +272,33 @@ def train_imitation(policy, supervisor="riccati_lqr", supervisor_config: dict | 
                 datasets.append((feats, targets))
             m = feats.shape[0]
             hist["size"].append(torch.tensor(m))
-            with torch.no_grad():
-                hist["before"].append(mse(feats, targets).to(torch.float64))
+            if hip is not None:
+                feats, targets = feats.contiguous(), targets.contiguous()
+                hist["before"].append(hip_loss(feats, targets))
+            else:
+                with torch.no_grad():
+                    hist["before"].append(mse(feats, targets).to(torch.float64))
             gen.manual_seed(int(seed) + e)
             order = torch.randperm(m, generator=gen, device=dev)
             for k in range(0, m, int(batch_size)):
                 idx = order[k:k + int(batch_size)]
-                loss = mse(feats.index_select(0, idx), targets.index_select(0, idx))
-                opt.zero_grad()
-                loss.backward()
+                if hip is not None:
+                    pack()
+                    hip.imitation_gradient(feats, targets, idx, imitation_weight, grad=flat_grad)
+                    for p, g in zip(params, grad_views):
+                        p.grad = g
+                else:
+                    loss = mse(feats.index_select(0, idx), targets.index_select(0, idx))
+                    opt.zero_grad()
+                    loss.backward()
                 if grad_clip > 0:
                     torch.nn.utils.clip_grad_norm_(net.parameters(), grad_clip)
                 opt.step()
-            with torch.no_grad():
-                hist["after"].append(mse(feats, targets).to(torch.float64))
+            if hip is not None:
+                hist["after"].append(hip_loss(feats, targets))
+            else:
+                with torch.no_grad():
+                    hist["after"].append(mse(feats, targets).to(torch.float64))
     finally:
         net.to(home)
     policy._batched = None  # compute_action packs the new weights

@@ -29,7 +29,18 @@
       per-step way to the same labels (policy action + teacher action +
       env.step, three launches per step), by the wall clock, best of 3.
 
-Each run prints one JSON line and appends it to --out when given.
+  python scripts/bench_policy.py --grad [--sizes 256,65536,2097152] [--passes 10]
+      The imitation loss and its gradient for minibatches drawn through an
+      index from a seeded synthetic data set of 2,097,152 pairs, one line per
+      size: (a) BatchedDeepPolicy.imitation_gradient (qt_policy_imitation_grad)
+      by HIP events, best of --passes; (b) what train_imitation's torch backend
+      does for the same minibatch (index_select, forward, mse_loss, zero_grad,
+      backward): at 256 by the wall clock between two synchronisations over
+      100 steps (host-bound, as --baseline), at the larger sizes by HIP events;
+      (c) the floor from the flop count, 3 x 2 x the multiply-adds per sample
+      at 157.3 TF.
+
+Each run prints one JSON line (--grad: one per size) and appends it to --out when given.
 """
 
 from __future__ import annotations
@@ -296,6 +307,75 @@ def baseline(args):
             "path": "torch.nn.Sequential + torch feature build + BatchedQuadcopterEnv.step, one step at a time"}
 
 
+def grad(args):
+    """(a) the HIP loss + gradient entry, (b) the torch backend's minibatch step without the optimiser,
+    (c) the flop floor; one line per minibatch size."""
+    import quadtrack
+
+    dev = torch.device("cuda:0")
+    net = network(dev, args.hidden).train()
+    sd = {}
+    for i in range(len(args.hidden)):
+        sd[f"feature_extractor.{2 * i}.weight"], sd[f"feature_extractor.{2 * i}.bias"] = net[2 * i].weight, net[2 * i].bias
+    sd["output_layer.weight"], sd["output_layer.bias"] = net[-1].weight, net[-1].bias
+    pol = quadtrack.BatchedDeepPolicy.from_state_dict(sd, args.hidden, "relu", device=dev)
+    rows = max(max(args.sizes), 1 << 21)
+    gen = torch.Generator(device=dev).manual_seed(0)
+    feats = torch.randn(rows, 18, generator=gen, device=dev, dtype=torch.float32) * 2.0
+    lo = torch.tensor([0.0, -3.0, -3.0, -3.0], device=dev)
+    scale = torch.tensor([20.0, 6.0, 6.0, 6.0], device=dev)
+    targets = torch.rand(rows, 4, generator=gen, device=dev, dtype=torch.float32) * scale + lo
+    params = list(net.parameters())
+
+    def torch_step(idx):  # train_imitation's torch backend up to the clip
+        loss = torch.nn.functional.mse_loss(torch.sigmoid(net(feats.index_select(0, idx))) * scale + lo,
+                                            targets.index_select(0, idx))
+        for p in params:
+            p.grad = None
+        loss.backward()
+        return loss
+
+    lines = []
+    for m in args.sizes:
+        idx = torch.randperm(rows, generator=gen, device=dev)[:m].contiguous()
+        out = torch.empty(sum(p.numel() for p in params), dtype=torch.float32, device=dev)
+        hip_ms, hip_all = _event_ms(lambda: pol.imitation_gradient(feats, targets, idx, 1.0, grad=out), lambda: None,
+                                    args.passes)
+        loss_hip = float(pol.imitation_gradient(feats, targets, idx, 1.0, grad=out)[0][0])
+        loss_torch = float(torch_step(idx))
+        flat = torch.cat([p.grad.reshape(-1) for p in params])
+        if m <= 4096:  # host-bound: wall clock over 100 steps between two synchronisations, best of 3
+            best = float("inf")
+            for _ in range(4):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                for _ in range(100):
+                    torch_step(idx)
+                torch.cuda.synchronize()
+                best = min(best, (time.perf_counter() - t0) * 10.0)  # ms per step
+            torch_ms, torch_timer = best, "wall clock over 100 steps between two synchronisations, best of 4"
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(100):
+                pol.imitation_gradient(feats, targets, idx, 1.0, grad=out)
+            torch.cuda.synchronize()
+            hip_wall = (time.perf_counter() - t0) * 10.0
+        else:
+            torch_ms, _ = _event_ms(lambda: torch_step(idx), lambda: None, args.passes)
+            torch_timer, hip_wall = "HIP events, best of passes", None
+        floor_ms = 3 * flops_per_step(args.hidden) * m / PEAK_F32 * 1e3
+        lines.append({"what": "policy_imitation_gradient", "network": f"{list(args.hidden)} relu", "samples": m,
+                      "passes": args.passes, "hip_ms_best": hip_ms, "hip_ms_all": hip_all,
+                      "hip_ms_wall_per_call": hip_wall, "torch_ms": torch_ms, "torch_timer": torch_timer,
+                      "torch_over_hip": torch_ms / (hip_wall if hip_wall is not None else hip_ms),
+                      "floor_ms": floor_ms, "hip_over_floor": hip_ms / floor_ms,
+                      "loss_hip": loss_hip, "loss_torch": loss_torch,
+                      "max_abs_grad_difference": float((flat - out).abs().max()),
+                      "max_abs_grad": float(flat.abs().max()),
+                      "timer": "HIP events around the three launches of the entry, best of passes"})
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--baseline", action="store_true")
@@ -310,16 +390,21 @@ def main():
                     help="population mode: members whose single-policy launches are timed and scaled (0: skip)")
     ap.add_argument("--supervised", action="store_true", help="the supervised rollout against its floor and the per-step way")
     ap.add_argument("--samples", type=int, default=32, help="supervised mode: sample slots per episode")
+    ap.add_argument("--grad", action="store_true", help="the imitation gradient against the torch backend's step")
+    ap.add_argument("--sizes", default="256,65536,2097152", help="--grad: minibatch sizes, comma-separated")
     args = ap.parse_args()
+    args.sizes = [int(v) for v in args.sizes.split(",")]
     args.hidden = [int(v) for v in args.hidden.split(",")]
     if args.steps is None:
         args.steps = 300 if args.baseline or args.members or args.supervised else 3000
     if args.passes is None:
         args.passes = 3 if args.baseline else 10
-    line = (supervised(args) if args.supervised else population(args) if args.members
+    line = (grad(args) if args.grad else supervised(args) if args.supervised else population(args) if args.members
             else baseline(args) if args.baseline else fused(args))
-    line["device"] = torch.cuda.get_device_name(0)
-    text = json.dumps(line)
+    lines = line if isinstance(line, list) else [line]
+    for ln in lines:
+        ln["device"] = torch.cuda.get_device_name(0)
+    text = "\n".join(json.dumps(ln) for ln in lines)
     print(text)
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
