@@ -351,10 +351,25 @@ int qt_rollout_rewards(const qt_env_params* env, const qt_ctrl_params* ctrl, con
    group's last wave (the group's loop with the stationary target selected per
    lane, the same numbers bit for bit), so N episodes take ceil(N / 64) waves
    when the stationary group can fill the other groups' gaps (round 6:
-   config 5's 8-GPU shard, 2,050 -> 2,048 waves). */
+   config 5's 8-GPU shard, 2,050 -> 2,048 waves).  Segment motions may repeat:
+   the riders come from the first non-empty stationary segment, and no
+   stationary segment hosts riders. */
 int qt_rollout_grouped(const qt_env_params* env, const qt_ctrl_params* ctrl, const qt_criteria* crit,
                        const qt_batch* batch, qt_state st, int32_t nsteps, double* rec, int32_t nseg,
                        const int32_t* seg_motion, const int64_t* seg_end, void* stream);
+
+/* (additive: QT_ABI_VERSION is unchanged.)  The slot layout the one-launch
+   grouped flavour of qt_rollout_grouped gives (seg_motion, seg_end), computed
+   by the code that lays out the launch; host only, nothing is launched (for
+   reports and tests).  seg_motion 0..4 (no mixed segment).  riders: 1 as with batch->motion given and riders on,
+   0 without.  *nseg_out: the non-empty segments.  At most 8: rows[6][8]
+   receives, per non-empty segment in slot order, seg_motion, seg_lo, seg_end,
+   ride_lo, ride_cnt and wave_end (its own slots [seg_lo, seg_end) and then the
+   riders [ride_lo, ride_lo + ride_cnt) fill its waves [wave_end[i-1],
+   wave_end[i])), and *waves the launch's waves.  More than 8: one launch set
+   per segment; rows is left alone and *waves is -1. */
+int qt_grouped_layout(int32_t nseg, const int32_t* seg_motion, const int64_t* seg_end, int32_t riders,
+                      int32_t* nseg_out, int64_t* rows, int64_t* waves);
 
 /* ABI 8.  One evaluation pass from reset to per-episode metrics: qt_reset
    (offset[3][n]), then qt_rollout (nsteps, no recording), then

@@ -108,8 +108,10 @@ struct BatchDev {
   // target (a fixed point) the group's loop forms by a per-lane select
   // (ride_target).  Group i's waves run its own slots [seg_lo[i], seg_end[i])
   // and then the riders [ride_lo[i], ride_lo[i] + ride_cnt[i]); the riders come
-  // from the front of the stationary group's slot range, whose own waves start
-  // after them (its seg_lo).  Slot ranges, and so slot_motion, are unchanged.
+  // from the front of the first stationary segment's slot range, whose own
+  // waves start after them (its seg_lo).  A stationary segment, the giving one
+  // or a repeated one, never hosts riders (ride_cnt 0: grouped_waves).  Slot
+  // ranges, and so slot_motion, are unchanged.
   int64_t seg_lo[8], ride_lo[8], ride_cnt[8];
   // A per-segment launch of a grouped batch (qt_rollout_grouped's one launch
   // set per group): the group's motion, which its slots' batch->motion must
@@ -1300,7 +1302,12 @@ __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(QT_GROUP
                                                                                     kExact, lc, slot);
       break;
 #endif
-    default:  // (no other key: rollout_batch gives a stationary group no riders)
+    default:
+      // no other key: grouped_waves (qt_rollout.hip) gives no stationary
+      // segment riders, the first one or a repeated one.  A wave that came
+      // here would not be stepped at all: the exact pass skips a wave whose
+      // lanes pass the wave test, whatever the deferred-wave flag says, so
+      // the layout rule alone keeps this case empty (tests/test_gpu_grouped_layouts.py)
       break;
   }
 }
@@ -1339,7 +1346,9 @@ void launch_fast(int flavor, bool uni, bool grouped, int kc, bool ff, bool ks, i
 
 // The pair-lane yaw-at-rest flavour (qt_pair.hpp; qt_rollout_fast.hip): one
 // episode on two lanes, for a batch of at most one wave per SIMD in pairs;
-// motion QT_MOTION_LINEAR or QT_MOTION_STATIONARY, grid of 2 n lanes.
+// motion: any of the five target motions (QT_MOTION_STATIONARY, LINEAR,
+// CIRCULAR, SINUSOIDAL, FIGURE8), the same for every episode; gains shared or
+// per episode (pair_fits, qt_rollout.hip); grid of 2 n lanes.
 void launch_pair(int motion, int grid, hipStream_t s, const qt_env_params& e, const qt_ctrl_params& c,
                  const qt_criteria& cr, const BatchDev& b, const qt_state& st, int nsteps, const LaunchConst& lc);
 

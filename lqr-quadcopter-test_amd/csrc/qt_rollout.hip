@@ -695,14 +695,39 @@ bool riders_on() {
 }
 
 // The waves of a one-launch grouped rollout (bg's segments: seg_motion,
-// seg_lo = previous seg_end, seg_end) and their wave_end.  With riders, the
-// first episodes of the stationary group fill the free lanes of every other
-// group's last wave, in group order, and the stationary group's own waves
+// seg_lo = previous seg_end, seg_end; rollout_batch lists the non-empty ones)
+// and their wave_end.  With riders, the first episodes of the first
+// stationary segment fill the free lanes of the last wave of every segment of
+// another motion, in segment order, and that stationary segment's own waves
 // start after them: a batch of N episodes then needs ceil(N / 64) waves
 // whenever the stationary group can fill the other groups' gaps (config 5's
 // 131,072-episode 8-GPU shard: 2,048 waves, the resident set at two waves per
-// SIMD, instead of 2,050).  Riders need per-episode motions (batch->motion):
-// the exact pass takes a deferred rider's motion from there.
+// SIMD, instead of 2,050).  No stationary segment hosts riders, the giving one
+// or a later one (segment motions may repeat): a stationary wave has no rider
+// select, and rollout_grouped_kernel has no loop for one with riders.
+// Riders need per-episode motions (batch->motion): the exact pass takes a
+// deferred rider's motion from there.  core.grouped_waves restates the rule;
+// tests/grouped_layout_ref.py's layout table is its test of record.
+// The non-empty segments of (seg_motion, seg_end) as bg's wave-aligned groups
+// (bg.nseg 0 on entry), without riders; false when there are more than the
+// one-launch form takes (bg is then left half filled and not used).
+bool grouped_segments(BatchDev& bg, int32_t nseg, const int32_t* seg_motion, const int64_t* seg_end) {
+  int64_t prev_end = 0;
+  for (int32_t i = 0; i < nseg; ++i) {
+    const int64_t cnt = seg_end[i] - prev_end;
+    if (cnt > 0) {
+      if (bg.nseg == 8) return false;
+      bg.seg_motion[bg.nseg] = (int8_t)seg_motion[i];
+      bg.seg_lo[bg.nseg] = prev_end;
+      bg.seg_end[bg.nseg] = seg_end[i];
+      bg.ride_lo[bg.nseg] = bg.ride_cnt[bg.nseg] = 0;
+      ++bg.nseg;
+    }
+    prev_end = seg_end[i];
+  }
+  return true;
+}
+
 int64_t grouped_waves(BatchDev& bg, bool riders) {
   int stat = -1;
   for (int i = 0; i < bg.nseg; ++i)
@@ -710,7 +735,7 @@ int64_t grouped_waves(BatchDev& bg, bool riders) {
   if (riders && stat >= 0) {
     int64_t next = bg.seg_lo[stat], avail = bg.seg_end[stat] - bg.seg_lo[stat];
     for (int i = 0; i < bg.nseg; ++i) {
-      if (i == stat) continue;
+      if (bg.seg_motion[i] == QT_MOTION_STATIONARY) continue;
       const int64_t gap = (64 - (bg.seg_end[i] - bg.seg_lo[i]) % 64) % 64;
       const int64_t take = gap < avail ? gap : avail;
       bg.ride_lo[i] = next, bg.ride_cnt[i] = take;
@@ -790,23 +815,7 @@ int rollout_batch(const qt_env_params& e, const qt_ctrl_params& c, const qt_crit
     // every group in one launch, each starting at a wavefront boundary (BatchDev's
     // wave-aligned segments; both the fast kernel and its exact pass map slots so)
     BatchDev bg = b;
-    int64_t prev_end = 0;
-    bool fits = true;
-    for (int32_t i = 0; i < nseg && fits; ++i) {
-      const int64_t cnt = seg_end[i] - prev_end;
-      if (cnt > 0) {
-        if (bg.nseg == 8) {
-          fits = false;
-          break;
-        }
-        bg.seg_motion[bg.nseg] = (int8_t)seg_motion[i];
-        bg.seg_lo[bg.nseg] = prev_end;
-        bg.seg_end[bg.nseg] = seg_end[i];
-        bg.ride_lo[bg.nseg] = bg.ride_cnt[bg.nseg] = 0;
-        ++bg.nseg;
-      }
-      prev_end = seg_end[i];
-    }
+    const bool fits = grouped_segments(bg, nseg, seg_motion, seg_end);
     const int64_t waves = fits ? grouped_waves(bg, QT_GROUPED_RIDERS && batch->motion != nullptr && riders_on()) : 0;
     if (fits) {
       // the grouped kernel has no fresh prologue / epilogue (rollout_lane's FRESH)
@@ -920,6 +929,30 @@ int qt_rollout_grouped(const qt_env_params* env, const qt_ctrl_params* ctrl, con
   if (prev != batch->n) return QT_EINVAL;
   if (batch->n == 0 || nsteps == 0) return QT_OK;
   return rollout_batch(*env, *ctrl, *crit, batch, st, nsteps, rec, nseg, seg_motion, seg_end, (hipStream_t)stream);
+}
+
+int qt_grouped_layout(int32_t nseg, const int32_t* seg_motion, const int64_t* seg_end, int32_t riders,
+                      int32_t* nseg_out, int64_t* rows, int64_t* waves) {
+  if (nseg < 0 || (nseg > 0 && (!seg_motion || !seg_end)) || !nseg_out || !rows || !waves) return QT_EINVAL;
+  int64_t prev = 0;
+  int32_t filled = 0;
+  for (int32_t i = 0; i < nseg; ++i) {  // qt_rollout_grouped's checks; a mixed segment (-1) has no one-launch layout
+    if (seg_end[i] < prev || seg_motion[i] < 0 || seg_motion[i] > 4) return QT_EINVAL;
+    filled += seg_end[i] > prev;
+    prev = seg_end[i];
+  }
+  *nseg_out = filled;
+  BatchDev bg{};
+  if (!grouped_segments(bg, nseg, seg_motion, seg_end)) {
+    *waves = -1;
+    return QT_OK;
+  }
+  *waves = grouped_waves(bg, QT_GROUPED_RIDERS && riders != 0);
+  for (int i = 0; i < bg.nseg; ++i) {
+    rows[0 * 8 + i] = bg.seg_motion[i], rows[1 * 8 + i] = bg.seg_lo[i], rows[2 * 8 + i] = bg.seg_end[i];
+    rows[3 * 8 + i] = bg.ride_lo[i], rows[4 * 8 + i] = bg.ride_cnt[i], rows[5 * 8 + i] = bg.wave_end[i];
+  }
+  return QT_OK;
 }
 
 int qt_rollout_fresh(const qt_env_params* env, const qt_ctrl_params* ctrl, const qt_criteria* crit,

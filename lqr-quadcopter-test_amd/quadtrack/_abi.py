@@ -163,7 +163,7 @@ def lean_bytes(n: int) -> int:
     return n * (LR_ROWS * 8 + FC_ROWS * 4 + FB_ROWS)
 
 
-EXPORTS = ("qt_abi_version", "qt_host_alloc", "qt_host_free", "qt_stream_sync", "qt_seed_draws", "qt_seed_uniform", "qt_reset", "qt_rollout", "qt_rollout_rewards", "qt_rollout_grouped", "qt_rollout_fresh",
+EXPORTS = ("qt_abi_version", "qt_host_alloc", "qt_host_free", "qt_stream_sync", "qt_seed_draws", "qt_seed_uniform", "qt_reset", "qt_rollout", "qt_rollout_rewards", "qt_rollout_grouped", "qt_grouped_layout", "qt_rollout_fresh",
            "qt_env_step", "qt_compute_action", "qt_target_state",
            "qt_episode_metrics", "qt_metrics_from_arrays", "qt_dare_batched", "qt_dare_dense", "qt_summary",
            "qt_summary_parts", "qt_summary_numpy", "qt_stream_uniform", "qt_frame_reset", "qt_frame_step",
@@ -199,6 +199,7 @@ def load():
     L.qt_rollout_rewards.argtypes = [P(EnvParams), P(CtrlParams), P(Criteria), P(Batch), State, i32, vp, vp]
     L.qt_rollout_grouped.argtypes = [P(EnvParams), P(CtrlParams), P(Criteria), P(Batch), State, i32, vp, i32,
                                      P(C.c_int32), P(C.c_int64), vp]
+    L.qt_grouped_layout.argtypes = [i32, P(C.c_int32), P(C.c_int64), i32, P(C.c_int32), P(C.c_int64), P(C.c_int64)]
     L.qt_rollout_fresh.argtypes = [P(EnvParams), P(CtrlParams), P(Criteria), P(Batch), vp, State, i32, vp, i32,
                                    P(C.c_int32), P(C.c_int64), vp]
     L.qt_seed_uniform.argtypes = [i64, vp, i32, vp, vp, vp, vp]

@@ -464,10 +464,11 @@ def riders_on() -> bool:
 def grouped_waves(seg_motion, seg_end, riders: bool | None = None) -> int:
     """The waves of the one-launch grouped rollout of a batch grouped as
     (seg_motion, seg_end) — qt_rollout.hip grouped_waves restated: with
-    riders, the first episodes of the stationary group fill the free lanes of
-    every other group's last wave, so the stationary group's own waves hold
-    only the rest.  (For reports and tests; the kernel's layout is the C
-    side's.)"""
+    riders, the first episodes of the first non-empty stationary segment fill
+    the free lanes of the last wave of every segment of another motion, so
+    that segment's own waves hold only the rest.  No stationary segment hosts
+    riders (segment motions may repeat).  (For reports and tests; the kernel's
+    layout is the C side's.)"""
     riders = riders_on() if riders is None else riders
     cnt, prev = [], 0
     for m, e in zip(seg_motion, seg_end):
@@ -479,12 +480,32 @@ def grouped_waves(seg_motion, seg_end, riders: bool | None = None) -> int:
         riders = False
     if riders and stat is not None:
         avail = cnt[stat][1]
-        for i, c in enumerate(cnt):
-            if i != stat:
+        for c in cnt:
+            if c[0] != 0:
                 take = min((64 - c[1] % 64) % 64, avail)
                 c[2], avail = take, avail - take
         cnt[stat][1] = avail
     return sum((own + rid + 63) // 64 for _, own, rid in cnt)
+
+
+def grouped_layout(seg_motion, seg_end, riders: bool = True):
+    """The C side's own one-launch layout of (seg_motion, seg_end)
+    (qt_grouped_layout: the code that lays out qt_rollout_grouped's launch;
+    host only, needs no GPU) -> (waves, rows): rows maps seg_motion, seg_lo,
+    seg_end, ride_lo, ride_cnt and wave_end to lists over the non-empty
+    segments.  More non-empty segments than the one-launch form takes:
+    (-1, None)."""
+    lib = _abi.load()
+    nseg = len(seg_motion)
+    sm = (C.c_int32 * max(nseg, 1))(*[int(v) for v in seg_motion])
+    se = (C.c_int64 * max(nseg, 1))(*[int(v) for v in seg_end])
+    rows, filled, waves = (C.c_int64 * 48)(), C.c_int32(), C.c_int64()
+    check(lib.qt_grouped_layout(nseg, sm, se, int(bool(riders)), C.byref(filled), rows, C.byref(waves)),
+          "qt_grouped_layout")
+    if waves.value < 0:
+        return -1, None
+    names = ("seg_motion", "seg_lo", "seg_end", "ride_lo", "ride_cnt", "wave_end")
+    return int(waves.value), {k: [int(rows[r * 8 + i]) for i in range(filled.value)] for r, k in enumerate(names)}
 
 
 def launch_waves(batch: EpisodeBatch) -> int:

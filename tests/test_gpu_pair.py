@@ -5,7 +5,10 @@ observation, accumulators — for every path the pair kernel takes: fresh
 passes, chunked launches (the accumulators and the lagged command-norm sum
 carried across launches), the stop vote and the exact finish (speed clamp,
 position bounds, time limit), waves deferred to the exact pass, ragged batch
-sizes, Euler, the stationary target.  One sample against the oracle as well.
+sizes, Euler, the stationary target; chunked launches of the periodic
+targets and of per-episode gains (tests/test_gpu_grouped_layouts.py's
+per-motion references run this flavour chunked, so it is pinned here).  One
+sample against the oracle as well.
 Reference loop: env/quadcopter_env.py:152-232, eval.py:119-165."""
 
 import numpy as np
@@ -124,27 +127,41 @@ def test_pair_flavour_bitwise_chunked(qt, monkeypatch):
     _same(a, b)
 
 
-def test_pair_flavour_deferred_waves(qt, monkeypatch):
-    """Episodes outside the yaw-at-rest preconditions (roll beyond the tilt
-    clamp): the pair kernel leaves their whole 64-episode waves to the exact
-    pass (the exact pass's wave test), which runs them; the same results as
-    the one-lane launch set, and as recording the exact step everywhere."""
-    from quadtrack import core
+@pytest.mark.parametrize("case", ["circular", "sinusoidal", "figure8", "config4"])
+def test_pair_flavour_bitwise_chunked_periodic(qt, monkeypatch, case):
+    """The chunked launches of the periodic targets: every launch derives the
+    target rotor again from the mid-episode t and rebuilds the target
+    acceleration row at its end.  1000 episodes with shared gains per target,
+    and a 384-episode config-4 shard (circular, per-episode gains)."""
+    from quadtrack import workloads
     from quadtrack.controllers import BatchedRiccatiLQR
-    from quadtrack.env.config import EnvConfig
+    from quadtrack.rollout import run_closed_loop
+
+    if case == "config4":
+        sh = workloads.build(4, 100000, 100000 + 384)
+        assert sh.controller.per_episode
+        ctl, kw = sh.controller, sh.run_kwargs()
+    else:
+        n = 1000
+        ctl, kw = BatchedRiccatiLQR({"dt": 0.01}), dict(env_config={"target": {"motion_type": case}}, n=n,
+                                                          seeds=np.arange(n))
+    a, b = _both(monkeypatch, lambda: run_closed_loop(ctl, chunk=137, **kw))
+    _same(a, b)
+
+
+def _deferred_waves(monkeypatch, ctl, cfg, n):
+    from quadtrack import core
+    from quadtrack.env.config import as_env_config
     from quadtrack.rollout import build_batch
 
-    n = 1000
-    ctl = BatchedRiccatiLQR({"dt": 0.01})
-    lin = {"target": {"motion_type": "linear"}}
-    env = EnvConfig.from_dict(lin).to_params()
+    env = as_env_config(cfg).to_params()
     crit = core.criteria()
 
     def run(record=False):
-        batch = build_batch(ctl, lin, n, seeds=np.arange(n))
+        batch = build_batch(ctl, cfg, n, seeds=np.arange(n))
         st = core.RolloutState.empty(n, batch.device)
         core.reset(env, batch, st)
-        for slot in (5, 100, 101, 999):  # waves 0, 1 and 15 (the last, partial) defer
+        for slot in (5, 100, 101, n - 1):  # waves 0, 1 and the last (partial) one defer
             st.x[6, slot] = 1.2
         for k in (150, 450):
             rec = torch.full((k, 16, n), float("nan"), dtype=torch.float64, device=batch.device) if record else None
@@ -158,6 +175,27 @@ def test_pair_flavour_deferred_waves(qt, monkeypatch):
     me, se = run(record=True)
     np.testing.assert_allclose(ma.cpu().numpy(), me.cpu().numpy(), rtol=1e-9, atol=1e-9)
     np.testing.assert_allclose(sa.x.cpu().numpy(), se.x.cpu().numpy(), rtol=1e-9, atol=1e-9)
+
+
+def test_pair_flavour_deferred_waves(qt, monkeypatch):
+    """Episodes outside the yaw-at-rest preconditions (roll beyond the tilt
+    clamp): the pair kernel leaves their whole 64-episode waves to the exact
+    pass (the exact pass's wave test), which runs them; the same results as
+    the one-lane launch set, and as recording the exact step everywhere."""
+    from quadtrack.controllers import BatchedRiccatiLQR
+
+    _deferred_waves(monkeypatch, BatchedRiccatiLQR({"dt": 0.01}), {"target": {"motion_type": "linear"}}, 1000)
+
+
+def test_pair_flavour_deferred_waves_per_episode_gains(qt, monkeypatch):
+    """The same with per-episode gains on a periodic target (a 1000-episode
+    config-4 shard): deferred waves, chunked launches and the per-episode gain
+    loads together."""
+    from quadtrack import workloads
+
+    sh = workloads.build(4, 100000, 100000 + 1000)
+    assert sh.controller.per_episode and sh.motion is None and sh.plant_mass is None
+    _deferred_waves(monkeypatch, sh.controller, sh.env_config, 1000)
 
 
 def test_pair_flavour_vs_oracle(qt, monkeypatch):

@@ -94,6 +94,119 @@ def test_grouped_waves_with_stationary_riders(monkeypatch):
     assert core.grouped_waves(*core.motion_groups(workloads.motion_of(0, 131072))[1:]) == 2050
 
 
+def _layout_table():
+    import grouped_layout_ref as G
+
+    return G
+
+
+@pytest.mark.parametrize("layout", list(_layout_table().LAYOUTS))
+def test_grouped_waves_layout_table(layout):
+    """core.grouped_waves over the layout table (tests/grouped_layout_ref.py):
+    the wave counts worked out by hand from the rider rule — riders come from
+    the first non-empty stationary segment and no stationary segment hosts
+    them — with riders and without."""
+    G = _layout_table()
+    sm, se = G.groups_of(G.LAYOUTS[layout])
+    assert (core.grouped_waves(sm, se, True), core.grouped_waves(sm, se, False)) == G.WAVES[layout]
+
+
+@pytest.mark.parametrize("layout", list(_layout_table().LAYOUTS))
+def test_grouped_waves_layout_bounds(layout):
+    """Riders never add a wave, and no layout needs fewer than ceil(n / 64)."""
+    G = _layout_table()
+    sm, se = G.groups_of(G.LAYOUTS[layout])
+    w = core.grouped_waves(sm, se, True)
+    assert -(-se[-1] // 64) <= w <= core.grouped_waves(sm, se, False)
+
+
+@pytest.mark.parametrize("riders", [True, False])
+@pytest.mark.parametrize("layout", list(_layout_table().LAYOUTS))
+def test_grouped_slot_map_visits_every_slot_once(layout, riders):
+    """qt_kernels.hpp slot_at restated (grouped_layout_ref.slot_at) over the
+    seg_lo / ride_lo / ride_cnt / wave_end of the rider rule: the launch
+    positions 0 .. 64 * waves - 1 visit every slot exactly once, a rider is a
+    stationary slot and never sits in a stationary wave, every other slot
+    sits in a wave of its own motion, and the wave count is
+    core.grouped_waves'.  More than eight non-empty segments have no
+    one-launch layout: one launch set per segment, each its own waves."""
+    G = _layout_table()
+    segs = G.LAYOUTS[layout]
+    sm, se = G.groups_of(segs)
+    n = se[-1]
+    lay = G.fixed_layout(segs, riders)
+    if lay is None:
+        assert sum(c > 0 for _, c in segs) > 8
+        assert core.grouped_waves(sm, se, riders) == sum(-(-c // 64) for _, c in segs)
+        return
+    assert lay.waves == core.grouped_waves(sm, se, riders) == G.WAVES[layout][0 if riders else 1]
+    pos = G.positions(lay)  # raises on a slot visited twice
+    assert sorted(pos) == list(range(n))
+    by_slot = G.slot_motions(segs)
+    for slot, (p, ride) in pos.items():
+        if ride:
+            assert riders and by_slot[slot] == G.STATIONARY and G.wave_motion(lay, p) != G.STATIONARY, (slot, p)
+        else:
+            assert G.wave_motion(lay, p) == by_slot[slot], (slot, p)
+
+
+def _c_side_agrees(G, segs, riders):
+    import dataclasses
+
+    sm, se = G.groups_of(segs)
+    waves, rows = core.grouped_layout(sm, se, riders)
+    lay = G.fixed_layout(segs, riders)
+    if lay is None:
+        assert (waves, rows) == (-1, None), segs
+        return None
+    assert rows == dataclasses.asdict(lay), (segs, riders)
+    assert waves == lay.waves == core.grouped_waves(sm, se, riders), (segs, riders)
+    return lay
+
+
+@pytest.mark.parametrize("riders", [True, False])
+@pytest.mark.parametrize("layout", list(_layout_table().LAYOUTS))
+def test_grouped_layout_c_side_is_the_rule(layout, riders):
+    """qt_grouped_layout (the host code that lays out qt_rollout_grouped's
+    launch, run without a GPU) over the table: seg_lo, ride_lo, ride_cnt and
+    wave_end are the restated rule's entry for entry, the waves
+    core.grouped_waves' and the table's."""
+    G = _layout_table()
+    lay = _c_side_agrees(G, G.LAYOUTS[layout], riders)
+    if lay is not None:
+        assert lay.waves == G.WAVES[layout][0 if riders else 1]
+
+
+def test_grouped_layout_c_side_random_segments():
+    """The same over 400 seeded layouts of 1 to 10 segments with repeated
+    motions and counts around the wave size (0, 1, 63, 64, 65, 127, 128 and
+    random ones): C side = restated rule = core.grouped_waves, and the slot
+    map visits every slot exactly once with riders only in waves of another
+    motion."""
+    import numpy as np
+
+    G = _layout_table()
+    rng = np.random.default_rng(15)
+    edge = [0, 1, 63, 64, 65, 127, 128]
+    for _ in range(400):
+        k = int(rng.integers(1, 11))
+        segs = [(int(rng.integers(0, 5)) if rng.random() < 0.7 else 0,
+                 int(rng.choice(edge)) if rng.random() < 0.5 else int(rng.integers(0, 300))) for _ in range(k)]
+        if sum(c for _, c in segs) == 0:
+            continue
+        for riders in (True, False):
+            lay = _c_side_agrees(G, segs, riders)
+            if lay is None:
+                continue
+            pos = G.positions(lay)
+            assert sorted(pos) == list(range(sum(c for _, c in segs))), segs
+            by_slot = G.slot_motions(segs)
+            for slot, (p, ride) in pos.items():
+                want_other = ride  # a rider sits in a wave of another motion, any other slot in one of its own
+                assert (G.wave_motion(lay, p) != by_slot[slot]) == want_other, (segs, slot, p)
+                assert not ride or by_slot[slot] == G.STATIONARY, (segs, slot, p)
+
+
 def test_pair_rounds_layout():
     """core.motion_groups with resident_waves (core.pair_rounds): a batch of
     one resident set has the group holding its middle wave split there at a
