@@ -105,7 +105,10 @@ __device__ bool sda_axis(double dt, double b, double qp, double qv, double qi, d
 #pragma unroll
       for (int i = k + 1; i < N; ++i)
         if (fabs(W[i][k]) > best) best = fabs(W[i][k]), p = i;
-      if (best == 0.0) return false;
+      if (best == 0.0) {
+        iters = it;
+        return false;
+      }
       if (p != k) {
 #pragma unroll
         for (int j = 0; j < N; ++j) {
@@ -172,13 +175,16 @@ __device__ bool sda_axis(double dt, double b, double qp, double qv, double qi, d
         H[i][j] = T[i][j];
         A[i][j] = nA[i][j];
       }
-    if (!isfinite(hn)) return false;
+    if (!isfinite(hn)) {
+      iters = it;
+      return false;
+    }
     if (sqrt(dn) <= kTol * sqrt(hn)) {
       conv = true;
       break;
     }
   }
-  iters = it;
+  iters = conv ? it : kMaxIter;  // doublings done: the loop leaves it at kMaxIter + 1 when none converged
   if (!conv) return false;
   // K = (r + b^2 P11)^-1 b (P A)[1, :]   (B has its only entry on the velocity row)
   const double den = r + b * b * H[1][1];
@@ -221,12 +227,14 @@ __global__ __launch_bounds__(256) void dare_axis_kernel(int64_t m, double dt, do
   auto qd = [&](int i) { return q[(int64_t)(i * NS + i) * m + pb]; };
   auto rd = [&](int i) { return r[(int64_t)(i * 4 + i) * m + pb]; };
   // _is_positive_semidefinite / _is_positive_definite on diagonal matrices:
-  // the eigenvalues are the diagonal entries.
+  // the eigenvalues are the diagonal entries.  Written so that a NaN weight
+  // fails the test it belongs to, as np.allclose(M, M.T) does in the
+  // reference and group_symmetric in the row kernel.
   bool qok = true, rok = true;
 #pragma unroll
-  for (int i = 0; i < NS; ++i) qok = qok && !(qd(i) < -1e-10);
+  for (int i = 0; i < NS; ++i) qok = qok && qd(i) >= -1e-10;
 #pragma unroll
-  for (int i = 0; i < 4; ++i) rok = rok && !(rd(i) <= 1e-10);
+  for (int i = 0; i < 4; ++i) rok = rok && rd(i) > 1e-10;
   const int st = !qok ? QT_DARE_Q_NOT_PSD : (!rok ? QT_DARE_R_NOT_PD : QT_DARE_OK);
   const double mss = mass ? mass[pb] : 1.0;
   // axis -> input row of K (thrust 0, roll 1, pitch 2) and B entry (riccati_lqr.py:248-261)
@@ -868,10 +876,6 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(QT_DARE_ROW_
   double ar[N];
 #pragma unroll
   for (int j = 0; j < N; ++j) ar[j] = a_in(j);
-  // the last doubling's |dH|_F^2 / |H|_F^2; NaN before the first doubling, so
-  // the quadratic test below always compares two measured changes (a first
-  // change that happens to be small proves nothing about the convergence rate)
-  double rel_prev = __builtin_nan("");
 
   // ---- doublings: W = I + G H ; Winv = W^-1 ; Y1 = Winv A ; Y2 = Winv G ;
   // H += sym(A' H Y1) ; G += sym(A Y2 A') ; A = A Y1, until |dH|_F <= tol |H|_F
@@ -963,16 +967,16 @@ __global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(QT_DARE_ROW_
     }
     dn = group_sum<GS>(r < N ? dn : 0.0);
     hn = group_sum<GS>(r < N ? hn : 0.0);
-    // |dH|_F <= tol |H|_F, squared (tol^2 = 1e-28: no square roots); or, in
-    // the doubling's quadratic regime (this change at most 4x the square of
-    // the last one, relative to |H|), a change below 1e-8 |H|: the next
-    // change, the error left in H, is then below ~1e-16 |H| (one doubling
-    // saved; a linearly converging problem, marginal modes with q_int = 0,
-    // never passes the quadratic test and runs to tol)
-    const double rel = dn / hn;
-    const bool quad = rel <= 1e-16 && rel <= 16.0 * rel_prev * rel_prev;
-    rel_prev = rel;
-    const int flag = !isfinite(hn) ? -1 : ((dn <= kTol * kTol * hn || quad) ? 1 : 0);
+    // |dH|_F <= tol |H|_F, squared (tol^2 = 1e-28: no square roots), as the
+    // axis kernel and the oracle stop.  No shortcut on top of it: an earlier
+    // version also stopped at a change below 1e-8 |H| that was at most 4x the
+    // square of the last one ("the quadratic regime, the next change is
+    // below 1e-16 |H|").  With weights many decades apart that holds for the
+    // heavy axis alone: its change collapses, what is left of |dH| is a light
+    // axis still far from converged, small against |H| and far below the
+    // square of the last change, and the solve stopped there (11 doublings
+    // instead of 29, a gain off by 1e-5; tests/test_gpu_dare_edges.py set W).
+    const int flag = !isfinite(hn) ? -1 : (dn <= kTol * kTol * hn ? 1 : 0);
     // M = A T2 ; G' = G + M (QT_DARE_SYM: + (M + M') / 2)
     if (QT_DARE_SYM) {
       bmul<N>(ar, t2, mm);
