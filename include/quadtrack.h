@@ -750,8 +750,8 @@ int qt_policy_supervised_rollout(const qt_env_params* env, const qt_ctrl_params*
    element.  No floating-point atomics: the same inputs give the same bits, in
    an order that depends on m alone.  Nothing is accumulated into grad, loss
    or the workspace: their previous contents do not matter.
-   Out of scope: the optimiser step and gradient clipping, a population form,
-   the tracking and control-effort loss terms. */
+   Out of scope: a population form, the tracking and control-effort loss terms
+   (gradient clipping and the optimiser step: qt_policy_optim_step below). */
 typedef struct qt_policy_grad_io {
   const float* features;   /* device, [rows][18] row-major */
   const float* targets;    /* device, [rows][4]  row-major */
@@ -779,6 +779,78 @@ int64_t qt_policy_grad_workspace(const qt_policy* policy, int64_t m);
    qt_policy_grad_workspace; a non-finite weight.  Three launches on `stream`,
    no host synchronisation. */
 int qt_policy_imitation_grad(const qt_policy* policy, const qt_policy_grad_io* io, void* stream);
+
+/* ---- clip + optimiser step and the fused imitation fit (additive:
+   QT_ABI_VERSION and the other version functions are unchanged, feature
+   detection goes through qt_policy_optim_version) ----
+   One minibatch update of the network's flat f32 parameter vector in ONE
+   launch (csrc/qt_policy_optim.hpp): clip_grad_norm_(params, max_norm), then
+   optimizer.step() of torch.optim.Adam, AdamW or SGD with momentum, then the
+   packed block of qt_policy rewritten from the new parameters.
+     norm  = (float)sqrt(sum_i (double)g_i^2), the sum in a fixed order
+     coef  = min(1, max_norm / (norm + 1e-6f)) in f32; g <- g * coef (max_norm <= 0: no clipping)
+     Adam  : g <- g + weight_decay theta;  m <- m + (g - m)(1 - beta1);
+             v <- v beta2 + (1 - beta2) g g;  t = *step + 1;
+             theta <- theta - (lr / (1 - beta1^t)) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps)
+     AdamW : theta <- theta (1 - lr weight_decay) first, no decay in g, then Adam
+     SGD   : g <- g + weight_decay theta;  m <- g at *step == 0, else m momentum + g;  theta <- theta - lr m
+   Every per-element operation is one IEEE f32 operation (division and square
+   root correctly rounded, nothing contracted); the scalars are formed in
+   double (the bias corrections on the device, from *step) and rounded to f32
+   once.  `grad` is not written; grad, theta, m, v and block must not overlap.
+   No floating-point atomics: the bits of every output are a function of the
+   inputs alone.
+   Out of scope: amsgrad, maximize, nesterov, dampening, learning-rate
+   schedules, a population form. */
+enum qt_optimizer { QT_OPT_ADAM = 0, QT_OPT_SGD = 1, QT_OPT_ADAMW = 2 };
+typedef struct qt_policy_optim {
+  int32_t kind, skip_nonfinite;   /* enum qt_optimizer; nonzero: a NaN or infinite norm skips the step */
+  double lr, weight_decay, beta1, beta2, eps, momentum, max_norm;  /* max_norm <= 0: no clipping */
+  float* theta;       /* device [flat size], parameters_to_vector order: the f32 master copy, read and written */
+  float* m; float* v; /* device [flat size]; SGD: m is the momentum buffer, v may be NULL */
+  int64_t* step;      /* device [1]: updates applied so far, read and incremented by the kernel */
+  int64_t* skipped;   /* device [1]: steps skipped (skip_nonfinite), incremented */
+  float* block;       /* device, QT_POLICY_BLOCK_FLOATS floats, may be NULL: rewritten whole from the new theta
+                         (padding: exact +0) */
+  float* grad_norm;   /* device [1], may be NULL: the total norm before clipping */
+} qt_policy_optim;
+
+/* 1: this library has qt_policy_optim_step and qt_policy_imitation_fit. */
+int qt_policy_optim_version(void);
+
+/* One launch on `stream`, no host synchronisation.  shape gives n_hidden,
+   width and activation (its params, lo and hi are not read).  A skipped step
+   (skip_nonfinite set and a NaN or infinite norm) leaves theta, m, v, *step
+   and block as they were and increments *skipped; grad_norm is written either
+   way.  QT_EINVAL before any launch: a NULL shape, opt, grad, theta, m, step
+   or skipped; a NULL v for Adam or AdamW; an invalid shape (qt_policy's
+   rules); an unknown kind; a non-finite or negative lr, weight_decay, eps or
+   momentum; a beta outside [0, 1); a NaN max_norm. */
+int qt_policy_optim_step(const qt_policy* shape, const qt_policy_optim* opt, const float* grad, void* stream);
+
+/* One pass over a data set in minibatches, enqueued from one call: for
+   minibatch k = 0, 1, ... the rows order[k batch .. min((k + 1) batch, m_total))
+   go through qt_policy_imitation_grad (index = that slice, loss = losses + k,
+   three launches) and then qt_policy_optim_step (one launch; its norm goes to
+   norms[k] when norms is given, else to opt->grad_norm).  The last minibatch
+   may be short.  No synchronisation between the steps: the results are those
+   of calling the two entries in turn. */
+typedef struct qt_policy_fit_io {
+  const float* features; const float* targets; int64_t rows;   /* as qt_policy_grad_io */
+  const int64_t* order;  int64_t m_total;  int64_t batch;      /* device [m_total] row numbers; minibatch k = order[k*batch .. ) */
+  double weight;
+  float* grad;            /* device [flat size] scratch */
+  double* losses;         /* device [ceil(m_total / batch)]: each minibatch's loss before its update */
+  float* norms;           /* device, same length, may be NULL */
+  void* workspace; int64_t workspace_bytes;                    /* qt_policy_grad_workspace(policy, min(batch, m_total)) */
+} qt_policy_fit_io;
+
+/* QT_EINVAL before the first launch: qt_policy_imitation_grad's and
+   qt_policy_optim_step's rules; a NULL order or losses; batch < 1 or
+   m_total < 1; a NULL opt->block or policy->params != opt->block (the
+   gradient must read the block the step rewrites). */
+int qt_policy_imitation_fit(const qt_policy* policy, const qt_policy_optim* opt, const qt_policy_fit_io* io,
+                            void* stream);
 
 #ifdef __cplusplus
 }

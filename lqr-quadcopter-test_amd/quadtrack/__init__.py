@@ -25,7 +25,7 @@ from .controllers import (
 )
 from .env import BatchedQuadcopterEnv, EnvConfig, QuadcopterEnv, TargetMotion
 from .eval import BatchedEvaluator, Evaluator, evaluate_batched, load_controller, run_hyperparameter_sweep
-from .policy import (PolicyPopulation, PopulationResult, SupervisedResult, evaluate_policy, evaluate_population,
+from .policy import (PolicyOptimizer, PolicyPopulation, PopulationResult, SupervisedResult, evaluate_policy, evaluate_population,
                      run_policy_loop, run_policy_population, run_policy_supervised)
 from .rollout import RolloutResult, run_closed_loop
 from .train import ImitationResult, SearchResult, search_policy, train_imitation
@@ -40,4 +40,4 @@ __all__ = ["BaseController", "BatchedLQR", "BatchedPID", "BatchedRiccatiLQR", "L
            "SuccessCriteria", "compute_episode_metrics", "_abi", "BatchedDeepPolicy", "DeepTrackingPolicy",
            "run_policy_loop", "evaluate_policy", "PolicyPopulation", "PopulationResult", "run_policy_population",
            "evaluate_population", "search_policy", "SearchResult", "run_policy_supervised", "SupervisedResult",
-           "train_imitation", "ImitationResult"]
+           "train_imitation", "ImitationResult", "PolicyOptimizer"]

@@ -120,6 +120,23 @@ class PolicyGradIO(C.Structure):
                 ("pred", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_int64)]
 
 
+class PolicyOptim(C.Structure):
+    """qt_policy_optim (additive; qt_policy_optim_version)"""
+
+    _fields_ = [("kind", C.c_int32), ("skip_nonfinite", C.c_int32)] + [
+        (k, C.c_double) for k in ("lr", "weight_decay", "beta1", "beta2", "eps", "momentum", "max_norm")] + [
+        (k, C.c_void_p) for k in ("theta", "m", "v", "step", "skipped", "block", "grad_norm")]
+
+
+class PolicyFitIO(C.Structure):
+    """qt_policy_fit_io (additive; qt_policy_optim_version)"""
+
+    _fields_ = [("features", C.c_void_p), ("targets", C.c_void_p), ("rows", C.c_int64), ("order", C.c_void_p),
+                ("m_total", C.c_int64), ("batch", C.c_int64), ("weight", C.c_double), ("grad", C.c_void_p),
+                ("losses", C.c_void_p), ("norms", C.c_void_p), ("workspace", C.c_void_p),
+                ("workspace_bytes", C.c_int64)]
+
+
 class PolicyObs(C.Structure):
     """qt_policy_obs"""
 
@@ -133,6 +150,8 @@ POLICY_VERSION = 1
 POLICY_POPULATION_VERSION = 1
 POLICY_SUPERVISED_VERSION = 1
 POLICY_GRAD_VERSION = 1
+POLICY_OPTIM_VERSION = 1
+OPTIMIZERS = {"adam": 0, "sgd": 1, "adamw": 2}  # enum qt_optimizer
 SUP_ROWS = 26  # QT_SUP_ROWS: 18 features, 4 teacher command, 4 policy command
 
 
@@ -170,7 +189,8 @@ EXPORTS = ("qt_abi_version", "qt_host_alloc", "qt_host_free", "qt_stream_sync", 
            "qt_compute_action_obs", "qt_frame_closed_step", "qt_lean_reset", "qt_lean_closed_step", "qt_lean_step",
            "qt_lean_expand", "qt_policy_version", "qt_policy_action", "qt_policy_rollout",
            "qt_policy_population_version", "qt_policy_population_rollout", "qt_policy_supervised_version",
-           "qt_policy_supervised_rollout", "qt_policy_grad_version", "qt_policy_imitation_grad")
+           "qt_policy_supervised_rollout", "qt_policy_grad_version", "qt_policy_imitation_grad",
+           "qt_policy_optim_version", "qt_policy_optim_step", "qt_policy_imitation_fit")
 
 _lib = None
 
@@ -235,6 +255,9 @@ def load():
     L.qt_policy_grad_workspace.argtypes = [P(Policy), i64]
     L.qt_policy_grad_workspace.restype = i64
     L.qt_policy_imitation_grad.argtypes = [P(Policy), P(PolicyGradIO), vp]
+    L.qt_policy_optim_version.argtypes = []
+    L.qt_policy_optim_step.argtypes = [P(Policy), P(PolicyOptim), vp, vp]
+    L.qt_policy_imitation_fit.argtypes = [P(Policy), P(PolicyOptim), P(PolicyFitIO), vp]
     for name in EXPORTS[1:]:
         getattr(L, name).restype = C.c_int
     v = L.qt_abi_version()
@@ -252,6 +275,11 @@ def has_policy_supervised() -> bool:
 def has_policy_grad() -> bool:
     """The loaded library has qt_policy_imitation_grad in this package's version."""
     return load().qt_policy_grad_version() == POLICY_GRAD_VERSION
+
+
+def has_policy_optim() -> bool:
+    """The loaded library has qt_policy_optim_step and qt_policy_imitation_fit in this package's version."""
+    return load().qt_policy_optim_version() == POLICY_OPTIM_VERSION
 
 
 def require_gpu(device=None) -> torch.device:

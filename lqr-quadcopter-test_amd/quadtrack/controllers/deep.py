@@ -412,8 +412,9 @@ class DeepTrackingPolicy(BaseController):
     Training: quadtrack.train.train_imitation fits self.network to a classical
     supervisor's commands (the reference trainer's imitation mode) on the
     supervised rollout, with torch autograd or the HIP backward pass
-    (backend="hip", BatchedDeepPolicy.imitation_gradient), and leaves the
-    weights here;
+    (backend="hip", BatchedDeepPolicy.imitation_gradient; backend="hip_fused":
+    the clip, the optimiser step and the packing on the device too,
+    PolicyOptimizer), and leaves the weights here;
     quadtrack.train.search_policy is the gradient-free search.  Weights may
     also come from the reference's trainer through a checkpoint.
 
@@ -687,3 +688,181 @@ class PolicyPopulation:
                                                            C.byref(batch.c_batch(with_k=False)), st.c_state(),
                                                            int(nsteps), _abi.ptr(rec), _abi.stream_of(self.device)),
                   "qt_policy_population_rollout")
+
+
+# ------------------------------------------------------------------ clip + optimiser step
+
+class PolicyOptimizer:
+    """The optimiser of imitation training on the device: clip_grad_norm_,
+    torch.optim.{Adam, AdamW, SGD(momentum=0.9)}.step() (the trainer's
+    optimisers, train.py:476-500, with torch's default betas and eps) and the
+    packing of the new weights, one launch per step (qt_policy_optim_step,
+    csrc/qt_policy_optim.hip).
+
+    policy      a DeepTrackingPolicy, a BatchedDeepPolicy or a config dict: the
+                shape, activation, output bounds and the starting weights
+    grad_clip   clip_grad_norm_'s max_norm; <= 0: no clipping
+    skip_nonfinite  a NaN or infinite gradient norm skips the step (counted in
+                `skipped`) instead of propagating into the weights
+
+    It owns, on the device: theta / m / v ([flat_size] float32,
+    parameters_to_vector order), step / skipped ([1] int64) and block (the
+    packed parameters).  `policy` is a BatchedDeepPolicy on that block: every
+    step rewrites it in place, so the policy always flies the current weights.
+    Nothing here synchronises with the host."""
+
+    def __init__(self, policy, optimizer: str = "adam", learning_rate: float = 1e-3, weight_decay: float = 0.0,
+                 grad_clip: float = 1.0, skip_nonfinite: bool = False, *, betas=(0.9, 0.999), eps: float = 1e-8,
+                 momentum: float = 0.9, device=None):
+        name = str(optimizer).lower()
+        if name not in _abi.OPTIMIZERS:
+            raise ValueError(f"Unknown optimizer: {name}")
+        hyper = {"learning_rate": float(learning_rate), "weight_decay": float(weight_decay), "eps": float(eps),
+                 "momentum": float(momentum)}
+        for k, x in hyper.items():
+            if not (np.isfinite(x) and x >= 0.0):
+                raise ValueError(f"{k} must be finite and >= 0, got {x}")
+        b1, b2 = (float(b) for b in betas)
+        if not (0.0 <= b1 < 1.0 and 0.0 <= b2 < 1.0):
+            raise ValueError(f"betas must lie in [0, 1), got {(b1, b2)}")
+        if np.isnan(float(grad_clip)):
+            raise ValueError("grad_clip must not be NaN")
+        if isinstance(policy, dict):
+            policy = DeepTrackingPolicy(policy, device="cpu")
+        if isinstance(policy, DeepTrackingPolicy):
+            net = policy.network
+            sizes, act, bounds = list(net.hidden_sizes), net.activation_name, net.output_bounds
+            dev = _abi.require_gpu(device if device is not None else
+                                   (policy.device if policy.device.type == "cuda" else None))
+            with torch.no_grad():
+                theta = torch.nn.utils.parameters_to_vector(net.parameters()).detach().to(dev, torch.float32).clone()
+        elif isinstance(policy, BatchedDeepPolicy):
+            sizes, act, bounds, dev = list(policy.hidden_sizes), policy.activation, policy.output_bounds, policy.device
+            theta = policy.params.index_select(0, PolicyPopulation._device_index(sizes, dev)[1])
+        else:
+            raise TypeError(f"expected a DeepTrackingPolicy, a BatchedDeepPolicy or a config dict, "
+                            f"got {type(policy).__name__}")
+        if not _abi.has_policy_optim():
+            raise ImportError("libquadtrack has another optimiser-step ABI than this package")
+        self.optimizer, self.hidden_sizes, self.device = name, sizes, dev
+        self.learning_rate, self.weight_decay = hyper["learning_rate"], hyper["weight_decay"]
+        self.betas, self.eps, self.momentum = (b1, b2), hyper["eps"], hyper["momentum"]
+        self.grad_clip, self.skip_nonfinite = float(grad_clip), bool(skip_nonfinite)
+        size = flat_size(sizes)
+        self.theta = theta.contiguous()
+        self.m = torch.zeros(size, dtype=torch.float32, device=dev)
+        self.v = torch.zeros(size, dtype=torch.float32, device=dev)
+        self.step_count = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.skipped = torch.zeros(1, dtype=torch.int64, device=dev)
+        self.grad_norm = torch.zeros(1, dtype=torch.float32, device=dev)
+        self.block = torch.empty(_abi.policy_block_floats(len(sizes), policy_tiles(sizes)), dtype=torch.float32,
+                                 device=dev)
+        self._grad = torch.empty(size, dtype=torch.float32, device=dev)
+        self._pack()
+        self.policy = BatchedDeepPolicy.from_block(self.block, sizes, act, bounds)
+        o = _abi.PolicyOptim()
+        o.kind, o.skip_nonfinite = _abi.OPTIMIZERS[name], int(self.skip_nonfinite)
+        o.lr, o.weight_decay, o.beta1, o.beta2 = self.learning_rate, self.weight_decay, b1, b2
+        o.eps, o.momentum, o.max_norm = self.eps, self.momentum, self.grad_clip
+        o.theta, o.m, o.v = self.theta.data_ptr(), self.m.data_ptr(), self.v.data_ptr()
+        o.step, o.skipped = self.step_count.data_ptr(), self.skipped.data_ptr()
+        o.block, o.grad_norm = self.block.data_ptr(), self.grad_norm.data_ptr()
+        self.c_optim = o
+        self._ref = C.byref(o)
+
+    def _pack(self) -> None:
+        """block from theta with torch's gather (construction and load_state_dict; a step packs in its launch)."""
+        gather, _ = PolicyPopulation._device_index(self.hidden_sizes, self.device)
+        src = torch.cat([self.theta, torch.zeros(1, dtype=torch.float32, device=self.device)])
+        torch.index_select(src, 0, gather, out=self.block)
+
+    def _want(self, t, name, shape, dtype):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a torch.Tensor, got {type(t).__name__}")
+        if t.device != self.device:
+            raise ValueError(f"{name} is on {t.device}, the optimiser on {self.device}")
+        if t.dtype != dtype:
+            raise ValueError(f"{name} must be {dtype}, got {t.dtype}")
+        if tuple(t.shape) != tuple(shape):
+            raise ValueError(f"{name} must have shape {list(shape)}, got {list(t.shape)}")
+        if not t.is_contiguous():
+            raise ValueError(f"{name} must be contiguous")
+
+    def step(self, grad: torch.Tensor) -> torch.Tensor:
+        """One update from a [flat_size] float32 gradient (imitation_gradient's;
+        it is not written).  Returns grad_norm ([1] float32, the norm before
+        clipping), which the next step overwrites."""
+        self._want(grad, "grad", (self.theta.numel(),), torch.float32)
+        with on_device(self.device):
+            check(_abi.load().qt_policy_optim_step(self.policy._ref, self._ref, grad.data_ptr(),
+                                                   raw_stream(self.device)), "qt_policy_optim_step")
+        return self.grad_norm
+
+    def fit(self, features: torch.Tensor, targets: torch.Tensor, order: torch.Tensor, batch_size: int,
+            weight: float = 1.0):
+        """One pass of minibatch steps enqueued by one call
+        (qt_policy_imitation_fit): minibatch k holds the rows
+        order[k * batch_size : (k + 1) * batch_size] of features / targets
+        ([rows, 18] / [rows, 4] float32; order: [m_total] int64 row numbers,
+        not checked), the last one possibly short; each takes
+        imitation_gradient's three launches and step's one.  Returns (losses
+        [steps] float64, each minibatch's loss before its update; norms [steps]
+        float32, its gradient norm before clipping), on the device."""
+        if not isinstance(features, torch.Tensor) or features.dim() != 2:
+            raise ValueError(f"features must be a [rows, {POLICY_INPUTS}] tensor")
+        rows = features.shape[0]
+        self._want(features, "features", (rows, POLICY_INPUTS), torch.float32)
+        self._want(targets, "targets", (rows, 4), torch.float32)
+        if not isinstance(order, torch.Tensor) or order.dim() != 1:
+            raise ValueError("order must be a one-dimensional int64 tensor")
+        m_total, batch = order.shape[0], int(batch_size)
+        self._want(order, "order", (m_total,), torch.int64)
+        if m_total < 1 or rows < 1 or batch < 1:
+            raise ValueError("fit needs at least one sample and a batch_size >= 1")
+        weight = float(weight)
+        if not np.isfinite(weight):
+            raise ValueError(f"weight must be finite, got {weight}")
+        lib = _abi.load()
+        widest = min(batch, m_total)
+        cache = self.policy.__dict__.setdefault("_grad_workspace", {})
+        ws = cache.get(widest)
+        if ws is None:
+            nbytes = lib.qt_policy_grad_workspace(self.policy._ref, widest)
+            if nbytes < 0:
+                raise ValueError(f"no gradient workspace for {widest} samples of this policy")
+            ws = cache[widest] = torch.empty((nbytes + 7) // 8, dtype=F64, device=self.device)
+        steps = -(-m_total // batch)
+        losses = torch.empty(steps, dtype=F64, device=self.device)
+        norms = torch.empty(steps, dtype=torch.float32, device=self.device)
+        io = _abi.PolicyFitIO()
+        io.features, io.targets, io.rows = features.data_ptr(), targets.data_ptr(), rows
+        io.order, io.m_total, io.batch, io.weight = order.data_ptr(), m_total, batch, weight
+        io.grad, io.losses, io.norms = self._grad.data_ptr(), losses.data_ptr(), norms.data_ptr()
+        io.workspace, io.workspace_bytes = ws.data_ptr(), ws.numel() * 8
+        with on_device(self.device):
+            check(lib.qt_policy_imitation_fit(self.policy._ref, self._ref, C.byref(io), raw_stream(self.device)),
+                  "qt_policy_imitation_fit")
+        return losses, norms
+
+    def state_dict(self) -> dict:
+        """Copies of the flat tensors and the two counters (device tensors)."""
+        return {"theta": self.theta.clone(), "m": self.m.clone(), "v": self.v.clone(),
+                "step": self.step_count.clone(), "skipped": self.skipped.clone()}
+
+    def load_state_dict(self, state: dict) -> None:
+        """state_dict's inverse (in place: the policy keeps its block)."""
+        size = self.theta.numel()
+        for k, t in (("theta", self.theta), ("m", self.m), ("v", self.v), ("step", self.step_count),
+                     ("skipped", self.skipped)):
+            src = torch.as_tensor(state[k])
+            if src.numel() != t.numel() or src.dtype != t.dtype:
+                raise ValueError(f"{k} must hold {size if t.numel() == size else 1} {t.dtype} values, "
+                                 f"got {src.dtype} {list(src.shape)}")
+        for k, t in (("theta", self.theta), ("m", self.m), ("v", self.v), ("step", self.step_count),
+                     ("skipped", self.skipped)):
+            t.copy_(torch.as_tensor(state[k]).reshape(t.shape))
+        self._pack()
+
+    def network_state_dict(self) -> dict:
+        """The current weights as a reference-format state dict (device copies)."""
+        return unflatten(self.theta.clone(), self.hidden_sizes)

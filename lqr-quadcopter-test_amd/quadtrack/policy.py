@@ -19,6 +19,11 @@ csrc/qt_policy_supervised.hip): the data source of imitation training
 `imitation_gradient` is that training's loss and gradient on the forward
 pass's MFMA path (`qt_policy_imitation_grad`, csrc/qt_policy_grad.hip): the
 backward pass of `train_imitation(..., backend="hip")`.
+
+`PolicyOptimizer` (controllers/deep.py) is that training's clip + optimiser
+step and packing in one launch (`qt_policy_optim_step`) and a whole minibatch
+pass enqueued by one call (`qt_policy_imitation_fit`,
+csrc/qt_policy_optim.hip): `train_imitation(..., backend="hip_fused")`.
 """
 
 from __future__ import annotations
@@ -29,8 +34,8 @@ import torch
 from . import _abi, core
 from dataclasses import dataclass
 
-from .controllers.deep import (BatchedDeepPolicy, DeepTrackingPolicy, PolicyPopulation, extract_features, pack_index,
-                               pack_params, policy_tiles)
+from .controllers.deep import (BatchedDeepPolicy, DeepTrackingPolicy, PolicyOptimizer, PolicyPopulation,
+                               extract_features, pack_index, pack_params, policy_tiles)
 from .env.batched import motion_indices
 from .env.config import as_env_config
 from .rollout import F64, RolloutResult, _criteria, build_batch, max_steps_for
@@ -39,7 +44,7 @@ from .utils.metrics import EvaluationSummary, SuccessCriteria
 __all__ = ["BatchedDeepPolicy", "DeepTrackingPolicy", "run_policy_loop", "evaluate_policy", "policy_batch",
            "pack_params", "policy_tiles", "extract_features", "PolicyPopulation", "PopulationResult", "pack_index",
            "run_policy_population", "evaluate_population", "run_policy_supervised", "SupervisedResult",
-           "sample_steps", "imitation_gradient"]
+           "sample_steps", "imitation_gradient", "PolicyOptimizer"]
 
 
 class _NoGains:

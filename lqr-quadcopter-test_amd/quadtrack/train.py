@@ -193,22 +193,39 @@ def train_imitation(policy, supervisor="riccati_lqr", supervisor_config: dict | 
     clip_grad_norm_ and torch optimiser; dataset_loss_before / after come from
     the same entry over the whole data set.  Nothing in the minibatch loop
     synchronises with the host.  The epoch's rollout, seeds and sampling are
-    the same under either backend.
+    the same under every backend.
+
+    backend="hip_fused" keeps the parameters, the optimiser state and the
+    packed block on the device in a PolicyOptimizer and runs the epoch's whole
+    minibatch pass as ONE call of qt_policy_imitation_fit
+    (csrc/qt_policy_optim.hip): per minibatch the gradient entry's three
+    launches and one launch that clips, steps the optimiser and repacks the
+    block, enqueued from C with no Python in between.  The same launch, seeds,
+    sampling, randperm order and dataset_loss_before / after as backend="hip";
+    the update's arithmetic is torch's formulas in f32 with the norm summed in
+    a fixed order, so the weights agree with backend="hip" to rounding, not
+    bit for bit.  The weights are copied back into policy.network at the end.
+    Measured per minibatch on 65,536 pairs (scripts/bench_policy.py --fit,
+    profiles/r17/policy_fit.jsonl): [64, 64] at batch 256 0.067 ms against
+    0.226 ms for backend="hip" and 0.618 ms for backend="torch"; at batch
+    4,096 0.085 / 0.231 / 0.627 ms; [128, 128, 128, 128] at batch 256 0.344 /
+    0.348 / 0.794 ms (the one-workgroup step takes 0.055 ms there: a tie).
 
     Out of scope: the tracking and control-effort terms of utils/losses.py
     (tracking_weight is taken as 0), curriculum, diagnostics, NaN recovery,
-    checkpoint cadence, the reward_weighted mode, a fused clip + optimiser
-    kernel (both stay torch's), a population form of the gradient, reading the
+    checkpoint cadence, the reward_weighted mode, learning-rate schedules,
+    graph capture of the fused pass, a population form of the gradient or of
+    the optimiser, reading the
     rollout's [S][26][n] sample block in place (the valid pairs are compacted
     first), and an exact host model of the gradient's summation order."""
-    from .controllers.deep import (BatchedDeepPolicy, DeepTrackingPolicy, PolicyPopulation, _bounds, flat_size,
-                                   policy_tiles, unflatten)
+    from .controllers.deep import (BatchedDeepPolicy, DeepTrackingPolicy, PolicyOptimizer, PolicyPopulation, _bounds,
+                                   flat_size, policy_tiles, unflatten)
     from .policy import _as_supervisor, run_policy_supervised
 
     if not isinstance(policy, DeepTrackingPolicy):
         raise TypeError(f"expected a DeepTrackingPolicy, got {type(policy).__name__}")
-    if backend not in ("torch", "hip"):
-        raise ValueError(f"Unknown backend: {backend}. Valid: 'torch', 'hip'")
+    if backend not in ("torch", "hip", "hip_fused"):
+        raise ValueError(f"Unknown backend: {backend}. Valid: 'torch', 'hip', 'hip_fused'")
     if epochs < 1 or episodes_per_epoch < 1 or batch_size < 1 or samples_per_episode < 1:
         raise ValueError("epochs, episodes_per_epoch, samples_per_episode and batch_size must be >= 1")
     net = policy.network
@@ -249,13 +266,22 @@ def train_imitation(policy, supervisor="riccati_lqr", supervisor_config: dict | 
             pack()
             return hip.imitation_gradient(f, y, None, imitation_weight, grad=flat_grad)[0][0]
 
+    fused = None
+    if backend == "hip_fused":
+        fused = PolicyOptimizer(policy, optimizer, learning_rate, weight_decay, grad_clip, device=dev)
+        hip = fused.policy
+        flat_grad = torch.empty(flat_size(list(net.hidden_sizes)), dtype=torch.float32, device=dev)
+
+        def hip_loss(f, y):  # the optimiser's block already holds the current parameters
+            return hip.imitation_gradient(f, y, None, imitation_weight, grad=flat_grad)[0][0]
+
     hist = {k: [] for k in ("reward", "ratio", "err", "imit", "before", "after", "size")}
     datasets = [] if keep_datasets else None
     gen = torch.Generator(device=dev)
     try:
         for e in range(epochs):
             E = int(episodes_per_epoch)
-            res = run_policy_supervised(policy.to_batched(dev), sup, env_config, n=E,
+            res = run_policy_supervised(hip if fused is not None else policy.to_batched(dev), sup, env_config, n=E,
                                         seeds=generation_seeds(env_seed, e, E), motion=motion, max_steps=max_steps,
                                         samples_per_episode=samples_per_episode, sample_seed=seed + e)
             st = res.state
@@ -280,7 +306,9 @@ def train_imitation(policy, supervisor="riccati_lqr", supervisor_config: dict | 
                     hist["before"].append(mse(feats, targets).to(torch.float64))
             gen.manual_seed(int(seed) + e)
             order = torch.randperm(m, generator=gen, device=dev)
-            for k in range(0, m, int(batch_size)):
+            if fused is not None:  # the whole pass from C; the Python loop below has nothing left to do
+                fused.fit(feats, targets, order, int(batch_size), imitation_weight)
+            for k in range(0, 0 if fused is not None else m, int(batch_size)):
                 idx = order[k:k + int(batch_size)]
                 if hip is not None:
                     pack()
@@ -299,6 +327,8 @@ def train_imitation(policy, supervisor="riccati_lqr", supervisor_config: dict | 
             else:
                 with torch.no_grad():
                     hist["after"].append(mse(feats, targets).to(torch.float64))
+        if fused is not None:
+            net.load_state_dict(fused.network_state_dict())
     finally:
         net.to(home)
     policy._batched = None  # compute_action packs the new weights

@@ -40,7 +40,17 @@
       (c) the floor from the flop count, 3 x 2 x the multiply-adds per sample
       at 157.3 TF.
 
-Each run prints one JSON line (--grad: one per size) and appends it to --out when given.
+  python scripts/bench_policy.py --fit [--pairs 65536] [--sizes 256,4096] [--passes 10]
+      One pass of Adam minibatch steps (clip 1.0) over a seeded synthetic data
+      set, one line per minibatch size, wall time per minibatch between two
+      synchronisations around the whole pass, best of --passes, the three
+      ways alternating inside every pass: (a) PolicyOptimizer.fit
+      (qt_policy_imitation_fit: four launches per minibatch enqueued from C),
+      (b) the minibatch loop of train_imitation(backend="hip") (pack,
+      imitation_gradient, .grad views, clip_grad_norm_, torch's Adam), (c) the
+      torch backend's loop (index_select, autograd, clip_grad_norm_, Adam).
+
+Each run prints one JSON line (--grad, --fit: one per size) and appends it to --out when given.
 """
 
 from __future__ import annotations
@@ -376,6 +386,103 @@ def grad(args):
     return lines
 
 
+def fit(args):
+    """(a) the fused pass, (b) the hip backend's minibatch loop, (c) the torch backend's; one line per batch size."""
+    import quadtrack
+    from quadtrack import _abi
+    from quadtrack.controllers.deep import PolicyPopulation, flat_size, policy_tiles, unflatten
+
+    dev = torch.device("cuda:0")
+    sizes, rows = list(args.hidden), args.pairs
+    gen = torch.Generator(device=dev).manual_seed(0)
+    feats = torch.randn(rows, 18, generator=gen, device=dev, dtype=torch.float32) * 2.0
+    lo = torch.tensor([0.0, -3.0, -3.0, -3.0], device=dev)
+    scale = torch.tensor([20.0, 6.0, 6.0, 6.0], device=dev)
+    targets = torch.rand(rows, 4, generator=gen, device=dev, dtype=torch.float32) * scale + lo
+    order = torch.randperm(rows, generator=gen, device=dev)
+    names = [f"feature_extractor.{2 * i}" for i in range(len(sizes))] + ["output_layer"]
+
+    def state_dict(net):
+        lin = [m for m in net if isinstance(m, torch.nn.Linear)]
+        return {f"{n}.{k}": getattr(m, k).detach() for n, m in zip(names, lin) for k in ("weight", "bias")}
+
+    def adam(net):
+        return torch.optim.Adam(net.parameters(), lr=1e-3)
+
+    lines = []
+    for batch in args.sizes:
+        # (a)
+        start = quadtrack.BatchedDeepPolicy.from_state_dict(state_dict(network("cpu", sizes)), sizes, "relu", device=dev)
+        fused_opt = quadtrack.PolicyOptimizer(start, "adam", learning_rate=1e-3, grad_clip=1.0)
+        # (b): train_imitation(backend="hip")'s minibatch loop
+        net_b = network(dev, sizes).train()
+        params_b, opt_b = list(net_b.parameters()), adam(net_b)
+        gather, _ = PolicyPopulation._device_index(sizes, dev)
+        src = torch.zeros(flat_size(sizes) + 1, dtype=torch.float32, device=dev)
+        block = torch.empty(_abi.policy_block_floats(len(sizes), policy_tiles(sizes)), dtype=torch.float32, device=dev)
+        flat_grad = torch.zeros(flat_size(sizes), dtype=torch.float32, device=dev)
+        hip = quadtrack.BatchedDeepPolicy.from_block(block, sizes, "relu")
+        views = unflatten(flat_grad, sizes)
+        grad_views = [views[f"{n}.{k}"] for n in names for k in ("weight", "bias")]
+
+        def pass_b():
+            for k in range(0, rows, batch):
+                idx = order[k:k + batch]
+                with torch.no_grad():
+                    torch.cat([p.reshape(-1) for p in params_b], out=src[:-1])
+                    torch.index_select(src, 0, gather, out=block)
+                hip.imitation_gradient(feats, targets, idx, 1.0, grad=flat_grad)
+                for p, g in zip(params_b, grad_views):
+                    p.grad = g
+                torch.nn.utils.clip_grad_norm_(params_b, 1.0)
+                opt_b.step()
+
+        # (c): the torch backend's loop
+        net_c = network(dev, sizes).train()
+        params_c, opt_c = list(net_c.parameters()), adam(net_c)
+
+        def pass_c():
+            for k in range(0, rows, batch):
+                idx = order[k:k + batch]
+                loss = torch.nn.functional.mse_loss(torch.sigmoid(net_c(feats.index_select(0, idx))) * scale + lo,
+                                                    targets.index_select(0, idx))
+                opt_c.zero_grad()
+                loss.backward()
+                torch.nn.utils.clip_grad_norm_(params_c, 1.0)
+                opt_c.step()
+
+        ways = {"fit": lambda: fused_opt.fit(feats, targets, order, batch), "hip_loop": pass_b, "torch_loop": pass_c}
+        steps = -(-rows // batch)
+        times = {k: [] for k in ways}
+        for _ in range(args.passes + 1):  # the first pass warms up
+            for k, run in ways.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                run()
+                torch.cuda.synchronize()
+                times[k].append((time.perf_counter() - t0) * 1e3 / steps)
+        best = {k: min(v[1:]) for k, v in times.items()}
+        # the clip + optimiser + pack launch alone: HIP events around 200 back-to-back steps, best of passes
+        g = torch.randn(flat_size(sizes), generator=gen, device=dev, dtype=torch.float32) * 1e-2
+
+        def steps_200():
+            for _ in range(200):
+                fused_opt.step(g)
+
+        step_ms = _event_ms(steps_200, lambda: None, args.passes)[0] / 200.0
+        lines.append({"what": "policy_imitation_fit", "network": f"{sizes} relu", "pairs": rows, "batch": batch,
+                      "steps_per_pass": steps, "passes": args.passes, "optimizer": "adam lr 1e-3, clip 1.0",
+                      "fit_ms_per_minibatch": best["fit"], "hip_loop_ms_per_minibatch": best["hip_loop"],
+                      "torch_loop_ms_per_minibatch": best["torch_loop"],
+                      "hip_loop_over_fit": best["hip_loop"] / best["fit"],
+                      "torch_loop_over_fit": best["torch_loop"] / best["fit"],
+                      "optim_step_ms_events_200_back_to_back": step_ms,
+                      "all_ms_per_minibatch": {k: [round(t, 5) for t in v[1:]] for k, v in times.items()},
+                      "timer": "wall clock between two synchronisations around one pass over the data set, "
+                               "divided by its minibatches; best of passes, the three ways alternating"})
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--baseline", action="store_true")
@@ -391,15 +498,18 @@ def main():
     ap.add_argument("--supervised", action="store_true", help="the supervised rollout against its floor and the per-step way")
     ap.add_argument("--samples", type=int, default=32, help="supervised mode: sample slots per episode")
     ap.add_argument("--grad", action="store_true", help="the imitation gradient against the torch backend's step")
-    ap.add_argument("--sizes", default="256,65536,2097152", help="--grad: minibatch sizes, comma-separated")
+    ap.add_argument("--sizes", default=None,
+                    help="--grad: minibatch sizes, comma-separated (default 256,65536,2097152); --fit: default 256,4096")
+    ap.add_argument("--fit", action="store_true", help="the fused minibatch pass against the hip and torch backends' loops")
+    ap.add_argument("--pairs", type=int, default=65536, help="--fit: pairs of the synthetic data set")
     args = ap.parse_args()
-    args.sizes = [int(v) for v in args.sizes.split(",")]
+    args.sizes = [int(v) for v in (args.sizes or ("256,4096" if args.fit else "256,65536,2097152")).split(",")]
     args.hidden = [int(v) for v in args.hidden.split(",")]
     if args.steps is None:
         args.steps = 300 if args.baseline or args.members or args.supervised else 3000
     if args.passes is None:
         args.passes = 3 if args.baseline else 10
-    line = (grad(args) if args.grad else supervised(args) if args.supervised else population(args) if args.members
+    line = (fit(args) if args.fit else grad(args) if args.grad else supervised(args) if args.supervised else population(args) if args.members
             else baseline(args) if args.baseline else fused(args))
     lines = line if isinstance(line, list) else [line]
     for ln in lines:
